@@ -8,12 +8,17 @@ for all of them to a verdict. Inputs (seeds) are generated on the device; all
 state is resident in HBM before the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--clusters C]
+                    [--dump-outputs DIR] [--full]
 For N > 1 the driver runs it under torch.distributed.run (one rank per GPU); run
 directly with --gpus N > 1 it starts that launcher itself as a child process.
-Rank 0 prints ONE JSON line. Besides the headline workload it times config 3's
-crash-restart + persister variant (`figure_8_unreliable_crash`: tests.rs:612-660's
-crash1/start1 in figure_8_unreliable's loop) on the same shard, reported under
-"variants".
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps of the
+headline workload and prints that line (its roofline record comes from the timed steps'
+own counters). With --dump-outputs DIR it also writes what the last timed step computed
+(every cluster's verdict code, verdict time and trace digest, and the step's counters) as
+DIR/<name>.npy. With --full it goes on to time config 3's crash-restart + persister variant
+(`figure_8_unreliable_crash`: tests.rs:612-660's crash1/start1 in figure_8_unreliable's loop)
+on the same shard and, for N = 1, config 3's whole 1M-cluster jobs, reported under
+"variants", and the CPU baseline (the oracle on the host cores).
 """
 import argparse
 import glob
@@ -163,6 +168,32 @@ def time_steps(bs, first_seed, total, warmup, steps, barrier):
     return time.perf_counter() - t0, acc
 
 
+def dump_outputs(d, batch, counters, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as float .npy files in `d`
+    (`<name>.npy`; `<name>_rank<r>.npy` for N > 1, every rank its own shard). The batch's
+    per-cluster verdicts (mr_batch_verdicts): `code` (u16) as float32, `time_us` (u32) as
+    float64, `digest` (u64) as [clusters, 2] float64 (high and low 32 bits, both exact); the
+    step's counters (mr_batch_finish) as float64: `counters` (the scalar fields in
+    MrCounters order), `cov_leaders`, `cov_events` (its verdict histogram follows from
+    `code`). The seeds follow from the arguments alone, so two runs with the same arguments
+    write the results of the same inputs."""
+    import numpy as np
+    code, t, dig = batch.verdicts()
+    names = [f for f, ty in _abi.MrCounters._fields_ if ty is _abi.C.c_uint64]
+    arrays = {
+        "code": code.astype(np.float32),
+        "time_us": t.astype(np.float64),
+        "digest": np.stack([dig >> np.uint64(32), dig & np.uint64(0xFFFFFFFF)], 1).astype(np.float64),
+        "counters": np.array([counters[f] for f in names], np.float64),
+        "cov_leaders": np.array(counters["cov_leaders"], np.float64),
+        "cov_events": np.array(counters["cov_events"], np.float64),
+    }
+    os.makedirs(d, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, arr in arrays.items():
+        np.save(os.path.join(d, f"{name}{sfx}.npy"), arr)
+
+
 def summed(acc):
     keys = ["events", "ev_msg", "ev_timer", "ev_tester", "msgs_sent", "drop_clog", "drop_loss",
             "drop_overflow", "entries_shipped", "log_writes", "entries_materialized", "applies",
@@ -183,16 +214,22 @@ def main():
     ap.add_argument("--nodes", type=int, default=0,
                     help="servers per cluster (0: the test's default; BASELINE config 4 runs the 2D "
                          "tests at 7)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last one's verdicts and counters as "
+                         "DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also time the --variant workload and the --million jobs "
+                         "and run the CPU baseline (a plain run does none of them)")
     ap.add_argument("--variant", default="figure_8_unreliable_crash",
-                    help="second workload timed on the same shard ('' = none)")
+                    help="--full: second workload timed on the same shard ('' = none)")
     ap.add_argument("--variant-steps", type=int, default=2)
     ap.add_argument("--million", type=int, default=1 << 20,
-                    help="N = 1 only: config 3's whole job (this many clusters) of the headline test and "
+                    help="--full, N = 1 only: config 3's whole job (this many clusters) of the headline test and "
                          "of its crash variant, each on this one GPU streaming through the resident pools "
                          "(0 = skip)")
     ap.add_argument("--cpu-seeds", type=int, default=320000,
-                    help="cpu_baseline sample: seeds in total, split over one process per core")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: cpu_baseline sample: seeds in total, split over one process per core")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-safety", action="store_true",
                     help="without the per-event Raft invariant checks (MR_F_SAFETY)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (RCCL) or gloo (one-GPU rehearsal)")
@@ -229,6 +266,8 @@ def main():
     n = int(bs[0].cfg.n_nodes)
     elapsed, acc = time_steps(bs, _abi.README_SEED, total, a.warmup, a.steps, barrier)
     kernel = bs[0].kernel  # mr_batch_kernel: the kernel the timed launches ran
+    if a.dump_outputs and a.steps > 0:  # the last timed step ran on bs[(steps - 1) % pipeline]
+        dump_outputs(a.dump_outputs, bs[(a.steps - 1) % len(bs)], acc[-1][1], rank, world)
     for b in bs:
         b.close()
     r0 = summed(acc)
@@ -304,7 +343,7 @@ def main():
         "alg_bytes_total": alg_bytes(tot, n),
         "lib_sha16": lib_sha,
     }
-    if a.variant:
+    if a.full and a.variant:
         bvs = [sim.Batch(a.variant, count, _abi.README_SEED, cluster_base=base, device=local,
                          safety=not a.no_safety) for _ in range(a.pipeline)]
         ev, accv = time_steps(bvs, _abi.README_SEED, total, 1, a.variant_steps, barrier)
@@ -324,7 +363,7 @@ def main():
             "pass_rate": round(sv["passed"] / max(sv["done"], 1), 6),
             "note": "config 3 read literally: crash1/start1 + persister (tests.rs:612-660) in "
                     "figure_8_unreliable's loop"}}
-    if world == 1 and a.million:
+    if a.full and world == 1 and a.million:
         # config 3 read at full size on ONE GPU (BASELINE.json configs[2]: 1M clusters, which the
         # driver's 8-GPU run shards 131,072 per GPU): the whole job as consecutive chunks of the
         # resident capacity, headline test and its crash-restart + persister variant. The on-hardware
@@ -341,7 +380,7 @@ def main():
                 "events_per_seed": round(sm["events"] / a.million, 1),
                 "pass_rate": round(sm["passed"] / max(sm["done"], 1), 6), "launches": sm["launches"],
                 "note": "config 3's whole job on one MI355X (streaming through the resident pools)"}
-    if world == 1 and not a.no_cpu_baseline:  # N = 1 only: the N > 1 lines are scaling points
+    if a.full and world == 1 and not a.no_cpu_baseline:  # N = 1 only: the N > 1 lines are scaling points
         # one process per host core this job may use (north_star): the CPUs it may run on, capped
         # by its cgroup CPU quota — on the GPU box 256 CPUs are visible but the quota is 16
         # cores, and 256 processes on 16 cores' time measured 38 % below 16 processes

@@ -20,8 +20,8 @@ def _run(args, timeout=240):
 
 
 def test_bench_single_rank_json():
-    d = _run([sys.executable, "bench.py", "--steps", "1", "--warmup", "0", "--clusters", "4096",
-              "--variant-steps", "1", "--no-cpu-baseline"])
+    d = _run([sys.executable, "bench.py", "--full", "--steps", "1", "--warmup", "0", "--clusters",
+              "4096", "--variant-steps", "1", "--no-cpu-baseline"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
               "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k
@@ -30,6 +30,37 @@ def test_bench_single_rank_json():
     assert d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1
     v = d["variants"]["figure_8_unreliable_crash"]
     assert v["value"] > 0 and v["pass_rate"] > 0.99
+
+
+def test_bench_plain_run_dumps_last_step(tmp_path):
+    """A plain run (no --full) times the headline only, and --dump-outputs writes the last
+    timed step's verdicts and counters as float arrays: those of the same seeds run on one
+    batch (step j of the run starts at seed README_SEED + j * clusters)."""
+    import numpy as np
+
+    from madraft_amd import _abi, sim
+    n, steps = 4096, 2
+    d = _run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", "1", "--clusters",
+              str(n), "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == steps and d["ms_per_step"] > 0
+    assert abs(d["value"] * d["ms_per_step"] / 1000 - n) < 1e-3 * n  # seeds/s * s per step
+    for k in ("variants", "cpu_baseline", "gpu_over_cpu"):
+        assert k not in d, k
+    got = {f[:-4]: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert sorted(got) == ["code", "counters", "cov_events", "cov_leaders", "digest", "time_us"]
+    assert got["code"].dtype == np.float32
+    assert all(v.dtype == np.float64 for k, v in got.items() if k != "code")
+    with sim.Batch("figure_8_unreliable_2c", n, safety=True) as b:
+        b.reset(_abi.README_SEED + steps * n)  # 1 warmup step + (steps - 1) timed ones before it
+        assert b.run()["remaining"] == 0
+        code, t, dig = b.verdicts()
+        c = b.counters()
+    assert np.array_equal(got["code"], code) and np.array_equal(got["time_us"], t)
+    assert np.array_equal(got["digest"][:, 0], dig >> np.uint64(32))
+    assert np.array_equal(got["digest"][:, 1], dig & np.uint64(0xFFFFFFFF))
+    names = [f for f, ty in _abi.MrCounters._fields_ if ty is _abi.C.c_uint64]
+    assert got["counters"].tolist() == [float(c[f]) for f in names]
+    assert got["cov_events"].tolist() == c["cov_events"]
 
 
 def test_bench_pipelined_steps_equal_sequential():

@@ -15,7 +15,7 @@ if has suite; then
   cat $O/smoke.txt
 fi
 if has bench; then
-  timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { echo "bench FAILED"; tail $O/bench.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { echo "bench FAILED"; tail $O/bench.err; exit 1; }
   cat $O/bench.json
   cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o run \
