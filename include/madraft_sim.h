@@ -39,87 +39,136 @@ extern "C" {
 #define MR_MAX_MSG_SLOTS 256u
 #define MR_MAX_AE 32u
 
-/* ---- scenarios: one id per reference #[madsim::test] (src/raft/tests.rs) ---- */
+/* ---- scenarios: one id per reference #[madsim::test] (src/raft/tests.rs) ----
+ * The one place that describes a scenario; enum mr_scenario, the names, mr_cfg_init's defaults, the
+ * kernel instances built and dispatched to and the Python mirror are generated from these rows:
+ *   X(id, SYMBOL, "test name", servers, kind, slots, exact, pool)
+ *   kind   RAFT, KV (kvraft generic_test and its variants) or CTRL (shard_ctrler)
+ *   slots  default mr_cfg.msg_slots: 32, 64, or 256 (clerks keep more than 64 messages in flight)
+ *   exact  server counts with a kernel instance of exactly that size: bit n set for n servers
+ *          (0x08 = 3, 0x20 = 5, 0x80 = 7); any other count runs the 8-server instance
+ *   pool   pool-kernel family built at those counts: NONE, RAFT (Raft-only test bodies without
+ *          spawned threads) or SVC (kvraft / shard_ctrler bodies)
+ * `exact` is a hex literal and `pool` a bare word so that _abi.py reads the rows as text. */
+#define MR_SCENARIO_TABLE(X) \
+  X(1, INITIAL_ELECTION_2A, "initial_election_2a", 3, RAFT, 32, 0x08, RAFT)   /* tests.rs:20-46   */ \
+  X(2, REELECTION_2A, "reelection_2a", 3, RAFT, 32, 0x08, RAFT)               /* tests.rs:48-78   */ \
+  X(3, MANY_ELECTION_2A, "many_election_2a", 7, RAFT, 32, 0x80, RAFT)         /* tests.rs:80-112  */ \
+  X(4, BASIC_AGREE_2B, "basic_agree_2b", 5, RAFT, 32, 0x20, RAFT)             /* tests.rs:114-130 */ \
+  X(5, FAIL_AGREE_2B, "fail_agree_2b", 3, RAFT, 32, 0x28, RAFT)               /* tests.rs:132-161 */ \
+  X(6, FAIL_NO_AGREE_2B, "fail_no_agree_2b", 5, RAFT, 32, 0x20, RAFT)         /* tests.rs:163-209 */ \
+  X(7, CONCURRENT_STARTS_2B, "concurrent_starts_2b", 3, RAFT, 32, 0x08, RAFT) /* tests.rs:211-275 */ \
+  X(8, REJOIN_2B, "rejoin_2b", 3, RAFT, 32, 0x08, RAFT)                       /* tests.rs:277-313 */ \
+  X(9, BACKUP_2B, "backup_2b", 5, RAFT, 32, 0x20, RAFT)                       /* tests.rs:315-386 */ \
+  X(10, COUNT_2B, "count_2b", 3, RAFT, 32, 0x08, RAFT)                        /* tests.rs:388-479 */ \
+  X(11, PERSIST1_2C, "persist1_2c", 3, RAFT, 32, 0x08, RAFT)                  /* tests.rs:481-526 */ \
+  X(12, PERSIST2_2C, "persist2_2c", 5, RAFT, 32, 0x20, RAFT)                  /* tests.rs:528-572 */ \
+  X(13, PERSIST3_2C, "persist3_2c", 3, RAFT, 32, 0x08, RAFT)                  /* tests.rs:574-602 */ \
+  X(14, FIGURE_8_2C, "figure_8_2c", 5, RAFT, 32, 0x20, RAFT)                  /* tests.rs:612-660 */ \
+  /* spawned tester threads (one() tasks, churn clients): no pool kernel */ \
+  X(15, UNRELIABLE_AGREE_2C, "unreliable_agree_2c", 5, RAFT, 32, 0x20, NONE)  /* tests.rs:662-686 */ \
+  X(16, FIGURE_8_UNRELIABLE_2C, "figure_8_unreliable_2c", 5, RAFT, 32, 0x20, RAFT) /* tests.rs:688-741 */ \
+  X(17, RELIABLE_CHURN_2C, "reliable_churn_2c", 5, RAFT, 32, 0x20, NONE)      /* tests.rs:743-747 */ \
+  X(18, UNRELIABLE_CHURN_2C, "unreliable_churn_2c", 5, RAFT, 32, 0x20, NONE)  /* tests.rs:749-753 */ \
+  X(19, SNAPSHOT_BASIC_2D, "snapshot_basic_2d", 3, RAFT, 32, 0x88, RAFT)      /* tests.rs:913-917 */ \
+  X(20, SNAPSHOT_INSTALL_2D, "snapshot_install_2d", 3, RAFT, 32, 0x88, RAFT)  /* tests.rs:919-923 */ \
+  X(21, SNAPSHOT_INSTALL_UNRELIABLE_2D, "snapshot_install_unreliable_2d", 3, RAFT, 32, 0x88, RAFT) /* tests.rs:925-929 */ \
+  X(22, SNAPSHOT_INSTALL_CRASH_2D, "snapshot_install_crash_2d", 3, RAFT, 32, 0x88, RAFT) /* tests.rs:931-935 */ \
+  X(23, SNAPSHOT_INSTALL_UNRELIABLE_CRASH_2D, "snapshot_install_unreliable_crash_2d", 3, RAFT, 32, 0x88, RAFT) /* tests.rs:937-941 */ \
+  /* BASELINE.json config 3 read literally: figure_8_unreliable_2c's loop with \
+   * crash1/start1 (figure_8_2c, tests.rs:638-649) in place of disconnect. */ \
+  X(24, FIGURE_8_UNRELIABLE_CRASH, "figure_8_unreliable_crash", 5, RAFT, 32, 0x20, RAFT) \
+  /* kvraft generic_test (src/kvraft/tests.rs:65-220) over 5 servers; BASELINE config 5 */ \
+  X(25, KV_BASIC_3A, "basic_3a", 5, KV, 64, 0x20, SVC)             /* kvraft/tests.rs:222-226: 1 client      */ \
+  X(26, KV_CONCURRENT_3A, "concurrent_3a", 5, KV, 64, 0x20, SVC)   /* kvraft/tests.rs:228-232: 5 clients     */ \
+  X(27, KV_UNRELIABLE_3A, "unreliable_3a", 5, KV, 64, 0x20, SVC)   /* kvraft/tests.rs:234-238: 5, unreliable */ \
+  /* shard_ctrler (src/shard_ctrler/tests.rs) over 3 servers */ \
+  X(28, CTRL_BASIC_4A, "basic_4a", 3, CTRL, 32, 0x08, SVC)         /* shard_ctrler/tests.rs:24-166  */ \
+  X(29, CTRL_MULTI_4A, "multi_4a", 3, CTRL, 32, 0x08, SVC)         /* shard_ctrler/tests.rs:168-299 */ \
+  /* kvraft generic_test with partitions / restarts (src/kvraft/tests.rs:344-385) */ \
+  X(30, KV_MANY_PARTITIONS_ONE_CLIENT_3A, "many_partitions_one_client_3a", 5, KV, 64, 0x20, SVC)     /* kvraft/tests.rs:344-348 */ \
+  X(31, KV_MANY_PARTITIONS_MANY_CLIENTS_3A, "many_partitions_many_clients_3a", 5, KV, 64, 0x20, SVC) /* kvraft/tests.rs:350-354 */ \
+  X(32, KV_PERSIST_ONE_CLIENT_3A, "persist_one_client_3a", 5, KV, 64, 0x20, SVC)                     /* kvraft/tests.rs:356-360 */ \
+  X(33, KV_PERSIST_CONCURRENT_3A, "persist_concurrent_3a", 5, KV, 64, 0x20, SVC)                     /* kvraft/tests.rs:362-366 */ \
+  X(34, KV_PERSIST_CONCURRENT_UNRELIABLE_3A, "persist_concurrent_unreliable_3a", 5, KV, 64, 0x20, SVC) /* kvraft/tests.rs:368-372 */ \
+  X(35, KV_PERSIST_PARTITION_3A, "persist_partition_3a", 5, KV, 64, 0x20, SVC)                       /* kvraft/tests.rs:374-378 */ \
+  X(36, KV_PERSIST_PARTITION_UNRELIABLE_3A, "persist_partition_unreliable_3a", 5, KV, 64, 0x20, SVC) /* kvraft/tests.rs:380-384 */ \
+  X(37, KV_UNRELIABLE_ONE_KEY_3A, "unreliable_one_key_3a", 3, KV, 64, 0x08, SVC)                     /* kvraft/tests.rs:240-274 */ \
+  X(38, KV_ONE_PARTITION_3A, "one_partition_3a", 5, KV, 64, 0x20, SVC)                               /* kvraft/tests.rs:276-342 */ \
+  /* kvraft 3B: services snapshot under maxraftstate = 1000 */ \
+  X(39, KV_SNAPSHOT_RPC_3B, "snapshot_rpc_3b", 3, KV, 64, 0x08, SVC)           /* kvraft/tests.rs:396-454 */ \
+  X(40, KV_SNAPSHOT_SIZE_3B, "snapshot_size_3b", 3, KV, 64, 0x08, SVC)         /* kvraft/tests.rs:456-492 */ \
+  X(41, KV_SNAPSHOT_RECOVER_3B, "snapshot_recover_3b", 5, KV, 64, 0x20, SVC)   /* kvraft/tests.rs:494-498 */ \
+  /* 20 clerks: 256 message slots and clerk hosts that do not fit the service pool */ \
+  X(42, KV_SNAPSHOT_RECOVER_MANY_CLIENTS_3B, "snapshot_recover_many_clients_3b", 5, KV, 256, 0x20, NONE) /* kvraft/tests.rs:500-504 */ \
+  X(43, KV_SNAPSHOT_UNRELIABLE_3B, "snapshot_unreliable_3b", 5, KV, 64, 0x20, SVC)                 /* kvraft/tests.rs:506-510 */ \
+  X(44, KV_SNAPSHOT_UNRELIABLE_RECOVER_3B, "snapshot_unreliable_recover_3b", 5, KV, 64, 0x20, SVC) /* kvraft/tests.rs:512-516 */ \
+  X(45, KV_SNAPSHOT_UNRELIABLE_RECOVER_CONCURRENT_PARTITION_3B, "snapshot_unreliable_recover_concurrent_partition_3b", 5, KV, 64, 0x20, SVC) /* kvraft/tests.rs:518-522 */ \
+  /* generic_test_linearizability (15 clients, 7 servers): the reference's commented-out \
+   * kvraft/tests.rs:386-390 and 524-528, defined by the build (docs/SEMANTICS.md §9b) */ \
+  X(46, KV_PERSIST_PARTITION_UNRELIABLE_LINEARIZABLE_3A, "persist_partition_unreliable_linearizable_3a", 7, KV, 64, 0x80, SVC) \
+  X(47, KV_SNAPSHOT_UNRELIABLE_RECOVER_CONCURRENT_PARTITION_LINEARIZABLE_3B, "snapshot_unreliable_recover_concurrent_partition_linearizable_3b", 7, KV, 64, 0x80, SVC)
+
+enum mr_scn_kind { MR_KIND_RAFT = 1, MR_KIND_KV = 2, MR_KIND_CTRL = 3 };  /* 0: no such scenario */
+enum mr_scn_pool { MR_POOL_FAMILY_NONE = 0, MR_POOL_FAMILY_RAFT = 1, MR_POOL_FAMILY_SVC = 2 };  /* = MR_POOL */
+
 enum mr_scenario {
   MR_SCN_NONE = 0,
-  MR_SCN_INITIAL_ELECTION_2A = 1,        /* tests.rs:20-46   */
-  MR_SCN_REELECTION_2A = 2,              /* tests.rs:48-78   */
-  MR_SCN_MANY_ELECTION_2A = 3,           /* tests.rs:80-112  */
-  MR_SCN_BASIC_AGREE_2B = 4,             /* tests.rs:114-130 */
-  MR_SCN_FAIL_AGREE_2B = 5,              /* tests.rs:132-161 */
-  MR_SCN_FAIL_NO_AGREE_2B = 6,           /* tests.rs:163-209 */
-  MR_SCN_CONCURRENT_STARTS_2B = 7,       /* tests.rs:211-275 */
-  MR_SCN_REJOIN_2B = 8,                  /* tests.rs:277-313 */
-  MR_SCN_BACKUP_2B = 9,                  /* tests.rs:315-386 */
-  MR_SCN_COUNT_2B = 10,                  /* tests.rs:388-479 */
-  MR_SCN_PERSIST1_2C = 11,               /* tests.rs:481-526 */
-  MR_SCN_PERSIST2_2C = 12,               /* tests.rs:528-572 */
-  MR_SCN_PERSIST3_2C = 13,               /* tests.rs:574-602 */
-  MR_SCN_FIGURE_8_2C = 14,               /* tests.rs:612-660 */
-  MR_SCN_UNRELIABLE_AGREE_2C = 15,       /* tests.rs:662-686 */
-  MR_SCN_FIGURE_8_UNRELIABLE_2C = 16,    /* tests.rs:688-741 */
-  MR_SCN_RELIABLE_CHURN_2C = 17,         /* tests.rs:743-747 */
-  MR_SCN_UNRELIABLE_CHURN_2C = 18,       /* tests.rs:749-753 */
-  MR_SCN_SNAPSHOT_BASIC_2D = 19,         /* tests.rs:913-917 */
-  MR_SCN_SNAPSHOT_INSTALL_2D = 20,       /* tests.rs:919-923 */
-  MR_SCN_SNAPSHOT_INSTALL_UNRELIABLE_2D = 21,       /* tests.rs:925-929 */
-  MR_SCN_SNAPSHOT_INSTALL_CRASH_2D = 22,            /* tests.rs:931-935 */
-  MR_SCN_SNAPSHOT_INSTALL_UNRELIABLE_CRASH_2D = 23, /* tests.rs:937-941 */
-  /* BASELINE.json config 3 read literally: figure_8_unreliable_2c's loop with
-   * crash1/start1 (figure_8_2c, tests.rs:638-649) in place of disconnect. */
-  MR_SCN_FIGURE_8_UNRELIABLE_CRASH = 24,
-  /* kvraft generic_test (src/kvraft/tests.rs:65-220) over 5 servers; BASELINE config 5 */
-  MR_SCN_KV_BASIC_3A = 25,               /* kvraft/tests.rs:222-226: 1 client        */
-  MR_SCN_KV_CONCURRENT_3A = 26,          /* kvraft/tests.rs:228-232: 5 clients       */
-  MR_SCN_KV_UNRELIABLE_3A = 27,          /* kvraft/tests.rs:234-238: 5, unreliable   */
-  /* shard_ctrler (src/shard_ctrler/tests.rs) over 3 servers */
-  MR_SCN_CTRL_BASIC_4A = 28,             /* shard_ctrler/tests.rs:24-166  */
-  MR_SCN_CTRL_MULTI_4A = 29,             /* shard_ctrler/tests.rs:168-299 */
-  /* kvraft generic_test with partitions / restarts (src/kvraft/tests.rs:344-385) */
-  MR_SCN_KV_MANY_PARTITIONS_ONE_CLIENT_3A = 30,    /* kvraft/tests.rs:344-348 */
-  MR_SCN_KV_MANY_PARTITIONS_MANY_CLIENTS_3A = 31,  /* kvraft/tests.rs:350-354 */
-  MR_SCN_KV_PERSIST_ONE_CLIENT_3A = 32,            /* kvraft/tests.rs:356-360 */
-  MR_SCN_KV_PERSIST_CONCURRENT_3A = 33,            /* kvraft/tests.rs:362-366 */
-  MR_SCN_KV_PERSIST_CONCURRENT_UNRELIABLE_3A = 34, /* kvraft/tests.rs:368-372 */
-  MR_SCN_KV_PERSIST_PARTITION_3A = 35,             /* kvraft/tests.rs:374-378 */
-  MR_SCN_KV_PERSIST_PARTITION_UNRELIABLE_3A = 36,  /* kvraft/tests.rs:380-384 */
-  MR_SCN_KV_UNRELIABLE_ONE_KEY_3A = 37,            /* kvraft/tests.rs:240-274 */
-  MR_SCN_KV_ONE_PARTITION_3A = 38,                 /* kvraft/tests.rs:276-342 */
-  /* kvraft 3B: services snapshot under maxraftstate = 1000 */
-  MR_SCN_KV_SNAPSHOT_RPC_3B = 39,                  /* kvraft/tests.rs:396-454 */
-  MR_SCN_KV_SNAPSHOT_SIZE_3B = 40,                 /* kvraft/tests.rs:456-492 */
-  MR_SCN_KV_SNAPSHOT_RECOVER_3B = 41,              /* kvraft/tests.rs:494-498 */
-  MR_SCN_KV_SNAPSHOT_RECOVER_MANY_CLIENTS_3B = 42, /* kvraft/tests.rs:500-504 */
-  MR_SCN_KV_SNAPSHOT_UNRELIABLE_3B = 43,           /* kvraft/tests.rs:506-510 */
-  MR_SCN_KV_SNAPSHOT_UNRELIABLE_RECOVER_3B = 44,   /* kvraft/tests.rs:512-516 */
-  MR_SCN_KV_SNAPSHOT_UNRELIABLE_RECOVER_CONCURRENT_PARTITION_3B = 45, /* kvraft/tests.rs:518-522 */
-  /* generic_test_linearizability (15 clients, 7 servers): the reference's commented-out
-   * kvraft/tests.rs:386-390 and 524-528, defined by the build (docs/SEMANTICS.md §9b) */
-  MR_SCN_KV_PERSIST_PARTITION_UNRELIABLE_LINEARIZABLE_3A = 46,
-  MR_SCN_KV_SNAPSHOT_UNRELIABLE_RECOVER_CONCURRENT_PARTITION_LINEARIZABLE_3B = 47,
-  MR_SCN_COUNT_
+#define MR_ROW_(id, sym, name, n, kind, slots, exact, pool) MR_SCN_##sym = id,
+  MR_SCENARIO_TABLE(MR_ROW_)
+#undef MR_ROW_
+  MR_SCN_COUNT_ /* 1 + the last row's id: rows stay in id order (checked in mr_dev.h) */
 };
 
+/* Column lookups by id (0 for an id without a row); constant expressions in C++, so the kernels'
+ * compile-time predicates (madraft_amd/csrc/mr_dev.h) read the same rows. */
+#ifdef __cplusplus
+#define MR_TABLE_FN_ static constexpr
+#else
+#define MR_TABLE_FN_ static inline
+#endif
+#define MR_COLUMN_(fn, ROW) \
+  MR_TABLE_FN_ uint32_t fn(uint32_t s) { switch (s) { MR_SCENARIO_TABLE(ROW) default: return 0; } }
+#define MR_ROW_N_(id, sym, name, n, kind, slots, exact, pool) case id: return n;
+#define MR_ROW_KIND_(id, sym, name, n, kind, slots, exact, pool) case id: return MR_KIND_##kind;
+#define MR_ROW_SLOTS_(id, sym, name, n, kind, slots, exact, pool) case id: return slots;
+#define MR_ROW_EXACT_(id, sym, name, n, kind, slots, exact, pool) case id: return exact;
+#define MR_ROW_POOL_(id, sym, name, n, kind, slots, exact, pool) case id: return MR_POOL_FAMILY_##pool;
+MR_COLUMN_(mr_scn_servers, MR_ROW_N_)
+MR_COLUMN_(mr_scn_kind, MR_ROW_KIND_)
+MR_COLUMN_(mr_scn_msg_slots, MR_ROW_SLOTS_)
+MR_COLUMN_(mr_scn_exact_mask, MR_ROW_EXACT_)
+MR_COLUMN_(mr_scn_pool, MR_ROW_POOL_)
+#undef MR_ROW_N_
+#undef MR_ROW_KIND_
+#undef MR_ROW_SLOTS_
+#undef MR_ROW_EXACT_
+#undef MR_ROW_POOL_
+#undef MR_COLUMN_
+
 /* kvraft scenarios (generic_test and its variants) */
-static inline int mr_scn_is_kv(uint32_t s) {
-  return (s >= MR_SCN_KV_BASIC_3A && s <= MR_SCN_KV_UNRELIABLE_3A) ||
-         (s >= MR_SCN_KV_MANY_PARTITIONS_ONE_CLIENT_3A &&
-          s <= MR_SCN_KV_SNAPSHOT_UNRELIABLE_RECOVER_CONCURRENT_PARTITION_LINEARIZABLE_3B);
-}
-/* default log / apply capacity of a kvraft scenario (no snapshots: every op stays in the log) */
+MR_TABLE_FN_ int mr_scn_is_kv(uint32_t s) { return mr_scn_kind(s) == MR_KIND_KV; }
 /* generic_test_linearizability scenarios (SEMANTICS §9b) */
-static inline int mr_scn_is_lin15(uint32_t s) {
+MR_TABLE_FN_ int mr_scn_is_lin15(uint32_t s) {
   return s == MR_SCN_KV_PERSIST_PARTITION_UNRELIABLE_LINEARIZABLE_3A ||
          s == MR_SCN_KV_SNAPSHOT_UNRELIABLE_RECOVER_CONCURRENT_PARTITION_LINEARIZABLE_3B;
 }
 /* scenarios whose clerks keep more than 64 messages in flight: 256 message slots */
-static inline int mr_scn_wide_slots(uint32_t s) { return s == MR_SCN_KV_SNAPSHOT_RECOVER_MANY_CLIENTS_3B; }
-static inline uint32_t mr_kv_log_cap(uint32_t s) {
-  if (s == MR_SCN_KV_SNAPSHOT_RECOVER_MANY_CLIENTS_3B) return 16384u;
-  return (s == MR_SCN_KV_BASIC_3A || s == MR_SCN_KV_UNRELIABLE_3A || s >= MR_SCN_KV_UNRELIABLE_ONE_KEY_3A ||
-          s == MR_SCN_KV_PERSIST_CONCURRENT_UNRELIABLE_3A || s == MR_SCN_KV_PERSIST_PARTITION_UNRELIABLE_3A ||
-          s == MR_SCN_KV_MANY_PARTITIONS_ONE_CLIENT_3A || s == MR_SCN_KV_PERSIST_ONE_CLIENT_3A) ? 2048u : 8192u;
+MR_TABLE_FN_ int mr_scn_wide_slots(uint32_t s) { return mr_scn_msg_slots(s) > 64u; }
+/* default log / apply capacity of a kvraft scenario (no snapshots: every op stays in the log),
+ * from the oracle's maxima: the bodies named here need more than 2048; 0 for any other id */
+MR_TABLE_FN_ uint32_t mr_kv_log_cap(uint32_t s) {
+  if (!mr_scn_is_kv(s)) return 0u;
+  switch (s) {
+    case MR_SCN_KV_SNAPSHOT_RECOVER_MANY_CLIENTS_3B: return 16384u;
+    case MR_SCN_KV_CONCURRENT_3A:
+    case MR_SCN_KV_MANY_PARTITIONS_MANY_CLIENTS_3A:
+    case MR_SCN_KV_PERSIST_CONCURRENT_3A:
+    case MR_SCN_KV_PERSIST_PARTITION_3A: return 8192u;
+    default: return 2048u;
+  }
 }
+#undef MR_TABLE_FN_
 
 /* ---- flags ---- */
 #define MR_F_UNRELIABLE 0x1u /* set_unreliable(true) right after RaftTester::new (C2) */
@@ -142,70 +191,78 @@ static inline uint32_t mr_kv_log_cap(uint32_t s) {
  * (mr_trace_digests) are what must catch it */
 #define MR_F_BUG_NO_APPLY_CHECK 0x800u
 
-/* ---- verdicts: one code per tester panic site ---- */
+/* ---- verdicts: one code per tester panic site ----
+ * X(code, SYMBOL, "message"): enum mr_fail { MR_<SYMBOL> = code }, mr_fail_message(code) and the
+ * Python mirror's FAIL_NAMES come from these rows. The comments cite the panic and, where the
+ * message shortens it, its format string. */
+#define MR_FAIL_TABLE(X) \
+  X(0, PASS, "ok") \
+  X(1, FAIL_ONE_LEADER_NONE, "expected one leader, got none")               /* tester.rs:91 */ \
+  X(2, FAIL_MULTI_LEADER_TERM, "term has (>1) leaders")                     /* tester.rs:83  "term {} has {:?} (>1) leaders" */ \
+  X(3, FAIL_TERM_DISAGREE, "servers disagree on term")                      /* tester.rs:105 */ \
+  X(4, FAIL_UNEXPECTED_LEADER, "expected no leader, but claims to be leader") /* tester.rs:119 "expected no leader, but {} claims..." */ \
+  X(5, FAIL_WAIT_TOO_FEW, "only decided for index; wanted more")            /* tester.rs:198 "only {} decided for index {}; wanted {}" */ \
+  X(6, FAIL_ONE_NO_AGREEMENT, "one() failed to reach agreement")            /* tester.rs:255,261 "one({:?}) failed to reach agreement" */ \
+  X(7, FAIL_TIMEOUT_120S, "test took longer than 120 seconds")              /* tester.rs:356 */ \
+  X(8, FAIL_APPLY_MISMATCH, "commit index mismatch between servers")        /* tester.rs:384-388 "commit index=.. server=.. != .." */ \
+  X(9, FAIL_APPLY_OUT_OF_ORDER, "server apply out of order")                /* tester.rs:393 "server {} apply out of order {}" */ \
+  X(10, FAIL_COMMIT_MISMATCH, "committed values do not match")              /* tester.rs:411-415 */ \
+  X(11, FAIL_UNWRAP_NONE, "called `Option::unwrap()` on a `None` value")    /* tester.rs:76,101,118,144,166 unwrap() on a crashed raft */ \
+  X(12, FAIL_LOG_SIZE, "log size too large")                                /* tests.rs:894 */ \
+  X(13, FAIL_BASIC_PRECOMMIT, "some have committed before start()")         /* tests.rs:123 */ \
+  X(14, FAIL_BASIC_INDEX, "got index but expected another")                 /* tests.rs:126 "got index {} but expected {}" */ \
+  X(15, FAIL_LEADER_REJECTED, "leader rejected start")                      /* tests.rs:180,202 (expect) */ \
+  X(16, FAIL_EXPECTED_INDEX2, "expected index 2")                           /* tests.rs:183 "expected index 2, got {}" */ \
+  X(17, FAIL_NO_MAJORITY_COMMIT, "committed but no majority")               /* tests.rs:189 "{} committed but no majority" */ \
+  X(18, FAIL_UNEXPECTED_INDEX, "unexpected index")                          /* tests.rs:204 "unexpected index {}" */ \
+  X(19, FAIL_CMD_MISSING, "cmd missing")                                    /* tests.rs:266 "cmd {} missing in {:?}" */ \
+  X(20, FAIL_TERM_CHANGED, "term changed too often")                        /* tests.rs:272,468 */ \
+  X(21, FAIL_RPC_INITIAL, "too many or few RPCs to elect initial leader")   /* tests.rs:397-401 */ \
+  X(22, FAIL_START_FAILED, "start failed")                                  /* tests.rs:434 */ \
+  X(23, FAIL_WRONG_VALUE, "wrong value committed")                          /* tests.rs:445-452 "wrong value {:?} committed..." */ \
+  X(24, FAIL_RPC_TOO_MANY, "too many RPCs for entries")                     /* tests.rs:462 "too many RPCs ({}) for {} entries" */ \
+  X(25, FAIL_RPC_IDLE, "too many RPCs for 1 second of idleness")            /* tests.rs:472-476 */ \
+  X(26, FAIL_CHURN_VALUE, "didn't find a value")                            /* tests.rs:852 */ \
+  X(27, FAIL_KV_GET_WRONG, "get wrong value")                               /* kvraft/tests.rs:127 "get wrong value, key {:?}" */ \
+  X(28, FAIL_KV_MISSING, "missing element in Append result")                /* kvraft/tests.rs:25-30 "missing element {:?} in Append result" */ \
+  X(29, FAIL_KV_APPEND_BAD, "duplicate or wrong order element in Append result") /* kvraft/tests.rs:31-39 */ \
+  X(30, FAIL_CTRL_NGROUPS, "assertion failed: c.groups.len() == groups.len()")   /* shard_ctrler/tester.rs:117 assert_eq!(c.groups.len(), ..) */ \
+  X(31, FAIL_CTRL_MISSING, "missing group")                                 /* shard_ctrler/tester.rs:120 "missing group {}" */ \
+  X(32, FAIL_CTRL_INVALID, "shard -> invalid group")                        /* shard_ctrler/tester.rs:125-130 "shard {} -> invalid group {}" */ \
+  X(33, FAIL_CTRL_IMBALANCED, "imbalanced sharding")                        /* shard_ctrler/tester.rs:142-148 */ \
+  X(34, FAIL_CTRL_SERVERS, "wrong servers for gid")                         /* shard_ctrler/tests.rs:51,53,198-202,210 */ \
+  X(35, FAIL_CTRL_HISTORY, "historical query differs")                      /* shard_ctrler/tests.rs:70 historical query != config */ \
+  X(36, FAIL_CTRL_MOVE_NUM, "Move should increase Tester.Num")              /* shard_ctrler/tests.rs:91 */ \
+  X(37, FAIL_CTRL_MOVE_WRONG, "shard wrong group")                          /* shard_ctrler/tests.rs:97 "shard {} wrong group" */ \
+  X(38, FAIL_CTRL_MINIMAL_JOIN, "non-minimal transfer after Join()s")       /* shard_ctrler/tests.rs:135,251 */ \
+  X(39, FAIL_CTRL_MINIMAL_LEAVE, "non-minimal transfer after Leave()s")     /* shard_ctrler/tests.rs:154,269 */ \
+  X(40, FAIL_CTRL_NO_LEADER, "Leader not found")                            /* shard_ctrler/tests.rs:282,289 */ \
+  X(41, FAIL_CTRL_SAME_CONFIG, "config differs after leader shutdown")      /* shard_ctrler/tests.rs:294 assert_eq!(c, c1) */ \
+  /* Raft invariants (MR_F_SAFETY; Raft paper Fig. 3), not reference panic sites */ \
+  X(42, FAIL_SAFETY_ELECTION, "election safety: two leaders in one term") \
+  X(43, FAIL_SAFETY_COMPLETENESS, "leader completeness: new leader lacks a committed entry") /* committed = applied */ \
+  X(44, FAIL_KV_LOG_SIZE, "logs were not trimmed")                          /* kvraft/tests.rs:208-215, :422-428, :475-481 */ \
+  X(45, FAIL_KV_SNAPSHOT_SIZE, "snapshot too large")                        /* kvraft/tests.rs:483-489 */ \
+  X(46, FAIL_KV_MINORITY_PROGRESS, "put/get in minority completed")         /* kvraft/tests.rs:315-319 */ \
+  X(47, FAIL_KV_NO_COMPLETION, "put/get did not complete")                  /* kvraft/tests.rs:333-337 */ \
+  X(48, FAIL_KV_CHECK, "get(key) check failed")                             /* kvraft/tester.rs:266-271 Clerk::check */ \
+  X(49, FAIL_SAFETY_LOG_MATCHING, "log matching: same index and term, different entries") /* MR_F_SAFETY */ \
+  /* the as-shipped service skeleton (MR_F_NULL_RAFT on kvraft / shard_ctrler tests) */ \
+  X(50, FAIL_TODO_APPLY, "not yet implemented: apply command")              /* kvraft/server.rs:69 */ \
+  X(51, FAIL_TODO_RPC_RESULTS, "not yet implemented: handle RPC results")   /* kvraft/client.rs:59 */ \
+  /* the build's linearizability checker (SEMANTICS §9a; the reference's are commented out, \
+   * kvraft/tests.rs:386-390,524-528): a Get's result fits no linearization of the key's history */ \
+  X(52, FAIL_KV_NOT_LINEARIZABLE, "history is not linearizable") \
+  /* simulator limits (not reference panics): a cluster that hits one is reported, never passed */ \
+  X(60, FAIL_SIM_CAPACITY, "simulator capacity exceeded")       /* a log / apply / sequence capacity of the config */ \
+  X(61, FAIL_SIM_EVENT_LIMIT, "simulator event limit exceeded") /* cfg.max_events processed without a verdict */ \
+  X(62, FAIL_SIM_BAD_PROGRAM, "scenario program error")         /* interpreter budget, bad op */ \
+  X(0xFFFF, RUNNING, "running")                                 /* verdict not reached yet */
+
 enum mr_fail {
-  MR_PASS = 0,
-  MR_FAIL_ONE_LEADER_NONE = 1,    /* tester.rs:91  "expected one leader, got none" */
-  MR_FAIL_MULTI_LEADER_TERM = 2,  /* tester.rs:83  "term {} has {:?} (>1) leaders" */
-  MR_FAIL_TERM_DISAGREE = 3,      /* tester.rs:105 "servers disagree on term" */
-  MR_FAIL_UNEXPECTED_LEADER = 4,  /* tester.rs:119 "expected no leader, but {} claims..." */
-  MR_FAIL_WAIT_TOO_FEW = 5,       /* tester.rs:198 "only {} decided for index {}; wanted {}" */
-  MR_FAIL_ONE_NO_AGREEMENT = 6,   /* tester.rs:255,261 "one({:?}) failed to reach agreement" */
-  MR_FAIL_TIMEOUT_120S = 7,       /* tester.rs:356 "test took longer than 120 seconds" */
-  MR_FAIL_APPLY_MISMATCH = 8,     /* tester.rs:384-388 "commit index=.. server=.. != .." */
-  MR_FAIL_APPLY_OUT_OF_ORDER = 9, /* tester.rs:393 "server {} apply out of order {}" */
-  MR_FAIL_COMMIT_MISMATCH = 10,   /* tester.rs:411-415 "committed values do not match" */
-  MR_FAIL_UNWRAP_NONE = 11,       /* tester.rs:76,101,118,144,166 unwrap() on a crashed raft */
-  MR_FAIL_LOG_SIZE = 12,          /* tests.rs:894 "log size too large" */
-  MR_FAIL_BASIC_PRECOMMIT = 13,   /* tests.rs:123 "some have committed before start()" */
-  MR_FAIL_BASIC_INDEX = 14,       /* tests.rs:126 "got index {} but expected {}" */
-  MR_FAIL_LEADER_REJECTED = 15,   /* tests.rs:180,202 "leader rejected start" (expect) */
-  MR_FAIL_EXPECTED_INDEX2 = 16,   /* tests.rs:183 "expected index 2, got {}" */
-  MR_FAIL_NO_MAJORITY_COMMIT = 17,/* tests.rs:189 "{} committed but no majority" */
-  MR_FAIL_UNEXPECTED_INDEX = 18,  /* tests.rs:204 "unexpected index {}" */
-  MR_FAIL_CMD_MISSING = 19,       /* tests.rs:266 "cmd {} missing in {:?}" */
-  MR_FAIL_TERM_CHANGED = 20,      /* tests.rs:272,468 "term changed too often" */
-  MR_FAIL_RPC_INITIAL = 21,       /* tests.rs:397-401 "too many or few RPCs..." */
-  MR_FAIL_START_FAILED = 22,      /* tests.rs:434 "start failed" */
-  MR_FAIL_WRONG_VALUE = 23,       /* tests.rs:445-452 "wrong value {:?} committed..." */
-  MR_FAIL_RPC_TOO_MANY = 24,      /* tests.rs:462 "too many RPCs ({}) for {} entries" */
-  MR_FAIL_RPC_IDLE = 25,          /* tests.rs:472-476 "too many RPCs for 1 second of idleness" */
-  MR_FAIL_CHURN_VALUE = 26,       /* tests.rs:852 "didn't find a value" */
-  MR_FAIL_KV_GET_WRONG = 27,      /* kvraft/tests.rs:127 "get wrong value, key {:?}" */
-  MR_FAIL_KV_MISSING = 28,        /* kvraft/tests.rs:25-30 "missing element {:?} in Append result" */
-  MR_FAIL_KV_APPEND_BAD = 29,     /* kvraft/tests.rs:31-39 duplicate / wrong order element */
-  MR_FAIL_CTRL_NGROUPS = 30,      /* shard_ctrler/tester.rs:117 assert_eq!(c.groups.len(), ..) */
-  MR_FAIL_CTRL_MISSING = 31,      /* shard_ctrler/tester.rs:120 "missing group {}" */
-  MR_FAIL_CTRL_INVALID = 32,      /* shard_ctrler/tester.rs:125-130 "shard {} -> invalid group {}" */
-  MR_FAIL_CTRL_IMBALANCED = 33,   /* shard_ctrler/tester.rs:142-148 "imbalanced sharding" */
-  MR_FAIL_CTRL_SERVERS = 34,      /* shard_ctrler/tests.rs:51,53,198-202,210 "wrong servers for gid" */
-  MR_FAIL_CTRL_HISTORY = 35,      /* shard_ctrler/tests.rs:70 historical query != config */
-  MR_FAIL_CTRL_MOVE_NUM = 36,     /* shard_ctrler/tests.rs:91 "Move should increase Tester.Num" */
-  MR_FAIL_CTRL_MOVE_WRONG = 37,   /* shard_ctrler/tests.rs:97 "shard {} wrong group" */
-  MR_FAIL_CTRL_MINIMAL_JOIN = 38, /* shard_ctrler/tests.rs:135,251 "non-minimal transfer after Join()s" */
-  MR_FAIL_CTRL_MINIMAL_LEAVE = 39,/* shard_ctrler/tests.rs:154,269 "non-minimal transfer after Leave()s" */
-  MR_FAIL_CTRL_NO_LEADER = 40,    /* shard_ctrler/tests.rs:282,289 "Leader not found" */
-  MR_FAIL_CTRL_SAME_CONFIG = 41,  /* shard_ctrler/tests.rs:294 assert_eq!(c, c1) */
-  /* Raft invariants (MR_F_SAFETY; Raft paper Fig. 3), not reference panic sites */
-  MR_FAIL_SAFETY_ELECTION = 42,   /* two leaders elected in one term */
-  MR_FAIL_SAFETY_COMPLETENESS = 43, /* a new leader lacks a committed (applied) entry */
-  MR_FAIL_KV_LOG_SIZE = 44,          /* kvraft/tests.rs:208-215, :422-428, :475-481 */
-  MR_FAIL_KV_SNAPSHOT_SIZE = 45,     /* kvraft/tests.rs:483-489 */
-  MR_FAIL_KV_MINORITY_PROGRESS = 46, /* kvraft/tests.rs:315-319 */
-  MR_FAIL_KV_NO_COMPLETION = 47,     /* kvraft/tests.rs:333-337 */
-  MR_FAIL_KV_CHECK = 48,             /* kvraft/tester.rs:266-271 Clerk::check */
-  MR_FAIL_SAFETY_LOG_MATCHING = 49,  /* MR_F_SAFETY: same index and term, different command */
-  /* the as-shipped service skeleton (MR_F_NULL_RAFT on kvraft / shard_ctrler tests) */
-  MR_FAIL_TODO_APPLY = 50,           /* kvraft/server.rs:69 "not yet implemented: apply command" */
-  MR_FAIL_TODO_RPC_RESULTS = 51,     /* kvraft/client.rs:59 "not yet implemented: handle RPC results" */
-  /* the build's linearizability checker (SEMANTICS §9a; the reference's are commented out,
-   * kvraft/tests.rs:386-390,524-528) */
-  MR_FAIL_KV_NOT_LINEARIZABLE = 52,  /* a Get's result fits no linearization of the key's history */
-  /* simulator limits (not reference panics): a cluster that hits one is reported, never passed */
-  MR_FAIL_SIM_CAPACITY = 60,      /* a log / apply / sequence capacity of the config was exceeded */
-  MR_FAIL_SIM_EVENT_LIMIT = 61,   /* cfg.max_events processed without a verdict */
-  MR_FAIL_SIM_BAD_PROGRAM = 62,   /* scenario program error (interpreter budget, bad op) */
-  MR_RUNNING = 0xFFFF             /* verdict not reached yet */
+#define MR_ROW_(code, sym, msg) MR_##sym = code,
+  MR_FAIL_TABLE(MR_ROW_)
+#undef MR_ROW_
 };
 
 typedef struct mr_cfg {

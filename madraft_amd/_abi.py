@@ -3,7 +3,10 @@
 Plain data definitions only; loading a library is done by madraft_amd.sim
 (the HIP product) or by the tests (the CPU oracle).
 """
+import collections
 import ctypes as C
+import os
+import re
 
 import numpy as np
 
@@ -37,60 +40,53 @@ def apply_mix(i, v):
 
 README_SEED = 1629626496  # /root/reference/README.md:48
 
-# enum mr_scenario, in header order (tests.rs names)
-SCENARIOS = [
-    "", "initial_election_2a", "reelection_2a", "many_election_2a", "basic_agree_2b",
-    "fail_agree_2b", "fail_no_agree_2b", "concurrent_starts_2b", "rejoin_2b", "backup_2b",
-    "count_2b", "persist1_2c", "persist2_2c", "persist3_2c", "figure_8_2c",
-    "unreliable_agree_2c", "figure_8_unreliable_2c", "reliable_churn_2c",
-    "unreliable_churn_2c", "snapshot_basic_2d", "snapshot_install_2d",
-    "snapshot_install_unreliable_2d", "snapshot_install_crash_2d",
-    "snapshot_install_unreliable_crash_2d", "figure_8_unreliable_crash", "basic_3a",
-    "concurrent_3a", "unreliable_3a", "basic_4a", "multi_4a",
-    "many_partitions_one_client_3a", "many_partitions_many_clients_3a", "persist_one_client_3a",
-    "persist_concurrent_3a", "persist_concurrent_unreliable_3a", "persist_partition_3a",
-    "persist_partition_unreliable_3a", "unreliable_one_key_3a", "one_partition_3a",
-    "snapshot_rpc_3b", "snapshot_size_3b", "snapshot_recover_3b", "snapshot_recover_many_clients_3b",
-    "snapshot_unreliable_3b", "snapshot_unreliable_recover_3b",
-    "snapshot_unreliable_recover_concurrent_partition_3b",
-    # generic_test_linearizability (15 clients, 7 servers; SEMANTICS §9b)
-    "persist_partition_unreliable_linearizable_3a",
-    "snapshot_unreliable_recover_concurrent_partition_linearizable_3b",
-]
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                      "include", "madraft_sim.h")
+_ROW = re.compile(r'\s*X\((\w+), (\w+), "((?:[^"\\]|\\.)*)"'
+                  r'(?:, (\d+), (\w+), (\d+), (0x[0-9A-Fa-f]+), (\w+))?\)')
+
+
+def _table(name):
+    """The rows of the header's X-macro `name`, fields as written: X(id, SYMBOL, "text"[, servers,
+    kind, slots, exact mask, pool]) up to the first line that does not continue."""
+    with open(HEADER) as f:
+        lines = f.read().split(f"#define {name}(X) \\\n", 1)[1].split("\n")
+    rows = []
+    for line in lines:
+        m = _ROW.match(line)
+        if m:
+            rows.append(m.groups())
+        elif line.lstrip().startswith("X("):
+            raise ValueError(f"{name}: cannot read the row {line.strip()!r}")
+        if not line.endswith("\\"):
+            break
+    return rows
+
+
+Scenario = collections.namedtuple("Scenario", "id symbol name servers kind slots exact pool")
+# MR_SCENARIO_TABLE: one row per scenario (exact: bit n = an n-server kernel instance is built;
+# pool: the pool-kernel family, NONE / RAFT / SVC)
+SCENARIO_ROWS = [Scenario(int(i), sym, name, int(n), kind, int(slots), int(exact, 16), pool)
+                 for i, sym, name, n, kind, slots, exact, pool in _table("MR_SCENARIO_TABLE")]
+SCENARIOS = [""] * (1 + max(r.id for r in SCENARIO_ROWS))  # enum mr_scenario -> tests.rs name
+for _r in SCENARIO_ROWS:
+    SCENARIOS[_r.id] = _r.name
 SCENARIO_ID = {n: i for i, n in enumerate(SCENARIOS) if n}
 # tests that still need multi-threaded tester programs (spawn_local); not built yet
 UNSUPPORTED = set()
 # kvraft generic_test (src/kvraft/tests.rs:65-238), BASELINE config 5
-KV_TESTS = ["basic_3a", "concurrent_3a", "unreliable_3a", "many_partitions_one_client_3a",
-            "many_partitions_many_clients_3a", "persist_one_client_3a", "persist_concurrent_3a",
-            "persist_concurrent_unreliable_3a", "persist_partition_3a",
-            "persist_partition_unreliable_3a", "unreliable_one_key_3a", "one_partition_3a",
-            "snapshot_rpc_3b", "snapshot_size_3b", "snapshot_recover_3b",
-            "snapshot_recover_many_clients_3b", "snapshot_unreliable_3b",
-            "snapshot_unreliable_recover_3b", "snapshot_unreliable_recover_concurrent_partition_3b",
-            "persist_partition_unreliable_linearizable_3a",
-            "snapshot_unreliable_recover_concurrent_partition_linearizable_3b"]
-LIN_TESTS = KV_TESTS[-2:]  # generic_test_linearizability (SEMANTICS §9b)
+KV_TESTS = [r.name for r in SCENARIO_ROWS if r.kind == "KV"]
+# generic_test_linearizability (SEMANTICS §9b): the symbols the header's mr_scn_is_lin15 names
+with open(HEADER) as _f:
+    _LIN15 = re.findall(r"MR_SCN_(\w+)", re.search(r"mr_scn_is_lin15\(uint32_t s\) \{(.*?)\n\}",
+                                                   _f.read(), re.S).group(1))
+LIN_TESTS = [r.name for r in SCENARIO_ROWS if r.symbol in _LIN15]
 GPU_UNSUPPORTED = set(UNSUPPORTED)
 
-FAIL_NAMES = {
-    0: "PASS", 1: "ONE_LEADER_NONE", 2: "MULTI_LEADER_TERM", 3: "TERM_DISAGREE",
-    4: "UNEXPECTED_LEADER", 5: "WAIT_TOO_FEW", 6: "ONE_NO_AGREEMENT", 7: "TIMEOUT_120S",
-    8: "APPLY_MISMATCH", 9: "APPLY_OUT_OF_ORDER", 10: "COMMIT_MISMATCH", 11: "UNWRAP_NONE",
-    12: "LOG_SIZE", 13: "BASIC_PRECOMMIT", 14: "BASIC_INDEX", 15: "LEADER_REJECTED",
-    16: "EXPECTED_INDEX2", 17: "NO_MAJORITY_COMMIT", 18: "UNEXPECTED_INDEX", 19: "CMD_MISSING",
-    20: "TERM_CHANGED", 21: "RPC_INITIAL", 22: "START_FAILED", 23: "WRONG_VALUE",
-    24: "RPC_TOO_MANY", 25: "RPC_IDLE", 26: "CHURN_VALUE", 27: "KV_GET_WRONG", 28: "KV_MISSING",
-    29: "KV_APPEND_BAD", 30: "CTRL_NGROUPS", 31: "CTRL_MISSING", 32: "CTRL_INVALID",
-    33: "CTRL_IMBALANCED", 34: "CTRL_SERVERS", 35: "CTRL_HISTORY", 36: "CTRL_MOVE_NUM",
-    37: "CTRL_MOVE_WRONG", 38: "CTRL_MINIMAL_JOIN", 39: "CTRL_MINIMAL_LEAVE", 40: "CTRL_NO_LEADER",
-    41: "CTRL_SAME_CONFIG", 42: "SAFETY_ELECTION", 43: "SAFETY_COMPLETENESS",
-    44: "KV_LOG_SIZE", 45: "KV_SNAPSHOT_SIZE", 46: "KV_MINORITY_PROGRESS", 47: "KV_NO_COMPLETION",
-    48: "KV_CHECK", 49: "SAFETY_LOG_MATCHING", 50: "TODO_APPLY", 51: "TODO_RPC_RESULTS",
-    52: "KV_NOT_LINEARIZABLE",
-    60: "SIM_CAPACITY",
-    61: "SIM_EVENT_LIMIT", 62: "SIM_BAD_PROGRAM", 0xFFFF: "RUNNING",
-}
+# MR_FAIL_TABLE: verdict code -> symbol without its MR_ / MR_FAIL_ prefix
+FAIL_NAMES = {int(code, 0): sym[5:] if sym.startswith("FAIL_") else sym
+              for code, sym, *_ in _table("MR_FAIL_TABLE")}
 
 
 class MrCfg(C.Structure):

@@ -9,6 +9,8 @@ import glob
 import os
 import subprocess
 
+from ._abi import SCENARIO_ID, SCENARIO_ROWS
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "lib", "libmadraft_hip.so")
@@ -16,7 +18,6 @@ LIB = os.path.join(HERE, "lib", "libmadraft_hip.so")
 # instances that use scratch or faulted once — count_2b, the churn tests (round 3's 8-server
 # fault was step_kernel<18, 8>), every kvraft / shard_ctrler test — and the headline
 GUARD_LIB = os.path.join(HERE, "lib", "libmadraft_guard.so")
-GUARD_SCNS = [10, 16, 17, 18] + list(range(25, 48))
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 
@@ -35,38 +36,32 @@ def _stale(out, srcs, key=""):
     return any(os.path.getmtime(s) > t for s in srcs)
 
 
+# The build's instance plan is read from the scenario table of include/madraft_sim.h (parsed by
+# _abi), the same rows mr_dev.h's has_exact / has_pool and the host's dispatch expand.
+ROWS = {r.id: r for r in SCENARIO_ROWS}
 # step-kernel instances (one per scenario id, mr_dev.h MR_ALL_SCNS) are split
 # over several translation units of mr_kernel.hip compiled in parallel
-SCN_IDS = list(range(1, 48))
+SCN_IDS = sorted(ROWS)
 N_GROUPS = 8
+DEFAULT_N = [ROWS[i].servers if i in ROWS else 0 for i in range(SCN_IDS[-1] + 1)]  # by id
 # scenarios whose kernels carry 256 message slots (snapshot_recover_many_clients_3b: up to
 # 229 messages in flight with 20 clerks)
-WIDE_SLOTS = {42}
-
-
-# scenarios with a 7-server instance too (mr_dev.h has_nb7: the 2D tests, BASELINE config 4)
-NB7_SCNS = {19, 20, 21, 22, 23}
-# the scenarios' default server counts (mr_dev.h k_default_n): each scenario
-# gets an instance sized for it (NB = 3 or 5) and one for up to 8 servers
-DEFAULT_N = [0, 3, 3, 7, 5, 3, 5, 3, 3, 5, 3, 3, 5, 3, 5, 5, 5, 5, 5, 3, 3, 3, 3, 3, 5, 5, 5, 5, 3, 3, 5, 5, 5, 5, 5, 5, 5, 3, 5, 3, 3, 5, 5, 5, 5, 5, 7, 7]
+WIDE_SLOTS = {i for i in SCN_IDS if ROWS[i].slots > 64}
+# pool-kernel units: unit name, the table's pool family, its -DMR_POOL value
+POOL_KINDS = (("pool", "RAFT", 1), ("svcpool", "SVC", 2))
+GUARD_SCNS = sorted({SCENARIO_ID[n] for n in ("count_2b", "figure_8_unreliable_2c",
+                                              "reliable_churn_2c", "unreliable_churn_2c")} |
+                    {i for i in SCN_IDS if ROWS[i].kind != "RAFT"})
 
 
 def has_exact(i, nb):
     """mr_dev.h has_exact: an exact-size instance (NB = n < 8) of scenario i is built."""
-    return nb < 8 and (DEFAULT_N[i] == nb or (i == 5 and nb == 5) or (i in NB7_SCNS and nb == 7))
-
-
-# Raft-only test bodies without spawned threads (mr_dev.h has_pool): the pool-kernel instances
-POOL_SCNS = set(range(1, 15)) | {16} | set(range(19, 25))
-# the kvraft / shard_ctrler test bodies (mr_dev.h is_svc): the service pool (MR_POOL=2), all but
-# the 20-clerk snapshot_recover_many_clients_3b (256 message slots)
-SVC_SCNS = set(range(25, 48))
-SVC_POOL_SCNS = SVC_SCNS - WIDE_SLOTS
+    return nb < 8 and bool(ROWS[i].exact >> nb & 1)
 
 
 def has_pool(i, nb):
     """mr_dev.h has_pool: a pool-kernel instance of scenario i at nb servers is built."""
-    return has_exact(i, nb) and ((nb <= 7 and i in POOL_SCNS) or i in SVC_POOL_SCNS)
+    return has_exact(i, nb) and ROWS[i].pool != "NONE"
 
 
 def _units(csrc, scns=None, tape=True):
@@ -90,9 +85,8 @@ def _units(csrc, scns=None, tape=True):
             units.append((kern, f"nb{nb}_w{i}", ["-DMR_COMMON=0", f"-DMR_SCN_LIST=MR_INST({i})",
                                                  f"-DMR_NB={nb}", "-DMR_MW=4", *key]))
     for nb in (3, 5, 7):  # pool kernels: 32-bit keys; Raft-only / service
-        for kind, pool in (("pool", 1), ("svcpool", 2)):
-            ids = [i for i in (scns or SCN_IDS)
-                   if has_pool(i, nb) and (i in SVC_POOL_SCNS) == (pool == 2)]
+        for kind, family, pool in POOL_KINDS:
+            ids = [i for i in (scns or SCN_IDS) if has_pool(i, nb) and ROWS[i].pool == family]
             ng = max(1, min(N_GROUPS, (len(ids) + 2) // 3)) if ids else 0
             for g in range(ng):
                 lst = " ".join(f"MR_INST({i})" for i in ids[g::ng])
@@ -127,7 +121,8 @@ def build_hip(force=False, verbose=False, extra=(), out=None, scns=None, csrc=No
     csrc = csrc or os.path.join(HERE, "csrc")
     srcs = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.cpp")))
     deps = srcs + glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.inc")) + \
-        [os.path.join(ROOT, "include", "madraft_sim.h"), os.path.abspath(__file__)]
+        [os.path.join(ROOT, "include", "madraft_sim.h"), os.path.abspath(__file__),
+         os.path.join(HERE, "_abi.py")]  # _abi reads the instance plan from the header
     key = repr((list(extra), sorted(scns) if scns else None, bool(tape), os.path.abspath(csrc), ARCH))
     if not force and not _stale(out, deps, key):
         return out

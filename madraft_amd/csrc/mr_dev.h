@@ -232,11 +232,25 @@ constexpr uint32_t PROF_SLOTS = 96;  // 64..94: pool_kernel statistics (MR_PROF,
 // later term is a simulator limit (MR_FAIL_SIM_CAPACITY); figure_8 peaks at term 177
 constexpr uint32_t LED_W = 64, LED_TERMS = 32 * LED_W;
 
+// The kind column of madraft_sim.h's MR_SCENARIO_TABLE. Device code calls nthr() (below) with the
+// template constant S but not in constant-evaluated contexts (`D.nthr = nthr(S)`), so an
+// out-of-line copy of it, and of these compares, is emitted into the code objects: they keep
+// their compare form, and every row is checked against them here.
 constexpr bool is_kv(uint32_t s) {
   return (s >= MR_SCN_KV_BASIC_3A && s <= MR_SCN_KV_UNRELIABLE_3A) ||
          (s >= MR_SCN_KV_MANY_PARTITIONS_ONE_CLIENT_3A &&
           s <= MR_SCN_KV_SNAPSHOT_UNRELIABLE_RECOVER_CONCURRENT_PARTITION_LINEARIZABLE_3B);
 }
+constexpr bool is_ctrl(uint32_t s) { return s == MR_SCN_CTRL_BASIC_4A || s == MR_SCN_CTRL_MULTI_4A; }
+// scenarios served by the clerk / server request path (kvraft + shard_ctrler)
+constexpr bool is_svc(uint32_t s) { return is_kv(s) || is_ctrl(s); }
+#define MR_ROW_(id, sym, name, n, kind, slots, exact, pool)                                \
+  static_assert(is_kv(id) == (MR_KIND_##kind == MR_KIND_KV) &&                             \
+                    is_ctrl(id) == (MR_KIND_##kind == MR_KIND_CTRL) && id < MR_SCN_COUNT_, \
+                name ": is_kv / is_ctrl disagree with the kind column, or rows out of id order");
+MR_SCENARIO_TABLE(MR_ROW_)
+#undef MR_ROW_
+static_assert(!is_svc(MR_SCN_NONE) && !is_svc(MR_SCN_COUNT_), "ids without a row are no service");
 // generic_test(nclients, unreliable, crash, partitions, maxraftstate) of a kvraft scenario
 // (kvraft/tests.rs:222-384, 494-522); snapshot_rpc / snapshot_size use maxraftstate too
 struct KvGen { uint32_t nc; bool unrel, crash, part; uint32_t maxraft; bool lin; };
@@ -281,9 +295,6 @@ constexpr bool ap_cont(uint32_t s) { return kv_gen(s).lin && kv_gen(s).maxraft =
 // snapshotting linearizable 3B body 89.7 K -> 93.6 K seeds/s with 8 (+4.4 %; 16: -5 %), the 5-client
 // 3B body 238 K -> 220 K (-7.5 %: its kernel spills the larger chunk)
 constexpr uint32_t kv_chunk(uint32_t s) { return kv_gen(s).lin ? 8u : 4u; }
-constexpr bool is_ctrl(uint32_t s) { return s == MR_SCN_CTRL_BASIC_4A || s == MR_SCN_CTRL_MULTI_4A; }
-// scenarios served by the clerk / server request path (kvraft + shard_ctrler)
-constexpr bool is_svc(uint32_t s) { return is_kv(s) || is_ctrl(s); }
 constexpr bool is_churn(uint32_t s) {
   return s == MR_SCN_RELIABLE_CHURN_2C || s == MR_SCN_UNRELIABLE_CHURN_2C;
 }
@@ -296,7 +307,7 @@ constexpr uint32_t nthr(uint32_t s) {
 }
 
 // step-kernel instances (mr_kernel.hip launch_step_t<S, NB>): per scenario, one
-// sized for its default server count (nb_of) and one for up to 8 servers
+// per exact server count (has_exact) and one for up to 8 servers
 template <uint32_t S, uint32_t NB>
 hipError_t launch_step_t(const Dev& D, uint32_t budget, hipStream_t s);
 // the pool kernel of scenario S (has_pool(S, NB); mr_kernel.hip MR_POOL units)
@@ -311,36 +322,38 @@ uint32_t step_capacity_t(int device, uint32_t M);
 // replay and record runs only, so the common draw path carries no tape branch
 template <uint32_t S, uint32_t NB>
 hipError_t launch_step_tape_t(const Dev& D, uint32_t budget, hipStream_t s);
-constexpr uint8_t k_default_n[] = {0, 3, 3, 7, 5, 3, 5, 3, 3, 5, 3, 3, 5, 3, 5,
-                                   5, 5, 5, 5, 3, 3, 3, 3, 3, 5, 5, 5, 5, 3, 3,
-                                   5, 5, 5, 5, 5, 5, 5, 3, 5, 3, 3, 5, 5, 5, 5, 5, 7, 7};
-constexpr uint32_t nb_of(uint32_t s) { return k_default_n[s] <= 5 ? k_default_n[s] : 8u; }
-// scenarios with a 7-server instance as well (BASELINE config 4 runs the 2D tests with 7
-// servers; arrays sized for 7 keep fewer registers live than the 8-server instance)
-constexpr bool has_nb7(uint32_t s) {
-  return s >= MR_SCN_SNAPSHOT_BASIC_2D && s <= MR_SCN_SNAPSHOT_INSTALL_UNRELIABLE_CRASH_2D;
-}
 // exact-size step-kernel instances (NB = n < 8): the node count is a compile-time constant there
 // (every `q < n` over the unrolled node loops folds away, and with it the loop-invariant lane
 // masks the compiler otherwise keeps in scalar registers); any other n runs the generic 8-server
-// instance. Built: each scenario at its default n, BASELINE config 2 (fail_agree_2b at 5
-// servers) and config 4 (the 2D tests at 7)
-constexpr bool has_exact(uint32_t s, uint32_t n) {
-  return n < 8u && (n == k_default_n[s] || (s == MR_SCN_FAIL_AGREE_2B && n == 5u) ||
-                    (has_nb7(s) && n == 7u));
-}
-// pool-kernel instances (mr_kernel.hip pool_kernel): Raft-only test bodies
-// without spawned threads at an exact server count of 3, 5 or 7 (512-cluster pools, up to 64
-// message slots: the 32-bit keys of slots 0..31 take 64 KiB of LDS, slots 32..63 — 7-server
-// bodies, BASELINE config 4 — keep theirs in HBM), and the kvraft / shard_ctrler test bodies at
-// their exact server count (256-cluster pools, up to 64 message slots, all keys in LDS; not the
-// 20-clerk snapshot_recover_many_clients_3b, whose 256 slots and clerk hosts do not fit)
+// instance. Built: the table's `exact` column — each scenario at its default n, BASELINE config 2
+// (fail_agree_2b at 5 servers) and config 4 (the 2D tests at 7: arrays sized for 7 keep fewer
+// registers live than the 8-server instance)
+constexpr bool has_exact(uint32_t s, uint32_t n) { return n < 8u && (mr_scn_exact_mask(s) >> n & 1u); }
+// pool-kernel instances (mr_kernel.hip pool_kernel), the table's `pool` column:
+// Raft-only test bodies without spawned threads at an exact server count of 3, 5 or 7
+// (512-cluster pools, up to 64 message slots: the 32-bit keys of slots 0..31 take 64 KiB of LDS,
+// slots 32..63 — 7-server bodies, BASELINE config 4 — keep theirs in HBM), and the kvraft /
+// shard_ctrler test bodies at their exact server count (256-cluster pools, up to 64 message
+// slots, all keys in LDS; not the 20-clerk snapshot_recover_many_clients_3b, whose 256 slots and
+// clerk hosts do not fit)
 constexpr bool has_pool(uint32_t s, uint32_t n) {
-  return has_exact(s, n) &&
-         ((n <= 7u && !is_svc(s) && nthr(s) == 0) ||
-          (is_svc(s) && s != MR_SCN_KV_SNAPSHOT_RECOVER_MANY_CLIENTS_3B));
+  return has_exact(s, n) && mr_scn_pool(s) != MR_POOL_FAMILY_NONE;
 }
 constexpr uint32_t pool_max_slots(uint32_t s, uint32_t n) { return is_svc(s) || n > 5u ? 64u : 32u; }
+// why a row may say what it says: a bad row fails here, not at the first launch
+#define MR_ROW_(id, sym, name, n, kind, slots, exact, pool)                                        \
+  static_assert(MR_POOL_FAMILY_##pool != MR_POOL_FAMILY_RAFT || (nthr(id) == 0 && !is_svc(id)),    \
+                name ": the Raft pool runs no spawned tester threads and no service");             \
+  static_assert(MR_POOL_FAMILY_##pool != MR_POOL_FAMILY_SVC || (is_svc(id) && slots <= 64),        \
+                name ": the service pool runs kvraft / shard_ctrler bodies of up to 64 slots");    \
+  static_assert(MR_POOL_FAMILY_##pool == MR_POOL_FAMILY_NONE || exact != 0,                        \
+                name ": pool kernels exist at exact server counts only");                          \
+  static_assert((exact & ~0xA8) == 0,                                                              \
+                name ": exact-size units are built and dispatched for 3, 5 and 7 servers (< 8)");  \
+  static_assert(n >= 3 && n <= MR_MAX_NODES && (n >= 8 || (exact >> n & 1)),                       \
+                name ": the default server count below 8 has its exact instance");
+MR_SCENARIO_TABLE(MR_ROW_)
+#undef MR_ROW_
 // scenarios whose test body starts the tester with service snapshots (t_new(snapshot = true),
 // tester.rs:303-325 SNAPSHOT_INTERVAL): snap_common's five 2D tests. node_apply_coop specializes
 // on it at compile time and checks it against the runtime mode (x.netmode bit 1).
@@ -360,13 +373,7 @@ constexpr bool restarts_servers(uint32_t s) {
          s == MR_SCN_UNRELIABLE_CHURN_2C || s == MR_SCN_SNAPSHOT_INSTALL_CRASH_2D ||
          s == MR_SCN_SNAPSHOT_INSTALL_UNRELIABLE_CRASH_2D || s == MR_SCN_FIGURE_8_UNRELIABLE_CRASH;
 }
-#define MR_ALL_SCNS                                                                       \
-  MR_INST(1) MR_INST(2) MR_INST(3) MR_INST(4) MR_INST(5) MR_INST(6) MR_INST(7) MR_INST(8) \
-  MR_INST(9) MR_INST(10) MR_INST(11) MR_INST(12) MR_INST(13) MR_INST(14) MR_INST(16)      \
-  MR_INST(19) MR_INST(20) MR_INST(21) MR_INST(22) MR_INST(23) MR_INST(24) MR_INST(25)     \
-  MR_INST(26) MR_INST(27) MR_INST(15) MR_INST(17) MR_INST(18) MR_INST(28) MR_INST(29)     \
-  MR_INST(30) MR_INST(31) MR_INST(32) MR_INST(33) MR_INST(34) MR_INST(35) MR_INST(36)     \
-  MR_INST(37) MR_INST(38) MR_INST(39) MR_INST(40) MR_INST(41) MR_INST(42) MR_INST(43)     \
-  MR_INST(44) MR_INST(45) MR_INST(46) MR_INST(47)
+#define MR_INST_ROW_(id, sym, name, n, kind, slots, exact, pool) MR_INST(id)
+#define MR_ALL_SCNS MR_SCENARIO_TABLE(MR_INST_ROW_)  // MR_INST(id) for every row of the table
 
 }  // namespace mr

@@ -16,82 +16,77 @@
 #include "mr_dev.h"
 
 namespace mr {
-// the step-kernel instance of scenario S for D.n servers: the exact-size one where it is built
-// (mr_dev.h has_exact), else the generic 8-server one
-template <uint32_t S>
-static hipError_t launch_any(const Dev& D, uint32_t budget, hipStream_t s) {
-#if MR_NO_TAPE  // a debug library without decision-tape kernels (build.build_guard)
-  if (D.tape_mode) return hipErrorInvalidValue;
-#else
-  if (D.tape_mode) return launch_step_tape_t<S, MR_MAX_NODES>(D, budget, s);
-#endif
-  if (D.pool) {  // the pool kernel (mr_dev.h has_pool; the host sets D.pool only where it exists)
-    if constexpr (has_pool(S, 3)) if (D.n == 3) return launch_pool_t<S, 3>(D, budget, s);
-    if constexpr (has_pool(S, 5)) if (D.n == 5) return launch_pool_t<S, 5>(D, budget, s);
-    if constexpr (has_pool(S, 7)) if (D.n == 7) return launch_pool_t<S, 7>(D, budget, s);
-    return hipErrorInvalidValue;
-  }
-  if constexpr (has_exact(S, 3)) if (D.n == 3) return launch_step_t<S, 3>(D, budget, s);
-  if constexpr (has_exact(S, 5)) if (D.n == 5) return launch_step_t<S, 5>(D, budget, s);
-  if constexpr (has_exact(S, 7)) if (D.n == 7) return launch_step_t<S, 7>(D, budget, s);
-  return launch_step_t<S, MR_MAX_NODES>(D, budget, s);
-}
-template <uint32_t S>
-static uint32_t capacity_any(const Dev& D, int device) {
-  if (D.pool) {
-    if constexpr (has_pool(S, 3)) if (D.n == 3) return pool_capacity_t<S, 3>(device, D.M);
-    if constexpr (has_pool(S, 5)) if (D.n == 5) return pool_capacity_t<S, 5>(device, D.M);
-    if constexpr (has_pool(S, 7)) if (D.n == 7) return pool_capacity_t<S, 7>(device, D.M);
-    return 0;
-  }
-  if constexpr (has_exact(S, 3)) if (D.n == 3) return step_capacity_t<S, 3>(device, D.M);
-  if constexpr (has_exact(S, 5)) if (D.n == 5) return step_capacity_t<S, 5>(device, D.M);
-  if constexpr (has_exact(S, 7)) if (D.n == 7) return step_capacity_t<S, 7>(device, D.M);
-  return step_capacity_t<S, MR_MAX_NODES>(device, D.M);
-}
-// the step-kernel instance of scenario `scn` (instances: MR_ALL_SCNS)
-hipError_t launch_step(const Dev& D, uint32_t scn, uint32_t budget, hipStream_t s) {
-  switch (scn) {
-#define MR_INST(S) \
-  case S: return launch_any<S>(D, budget, s);
-#ifdef MR_DEV_SCNS  // dev variants built for a few scenarios (build.py scns=)
-    MR_DEV_SCNS
-#else
-    MR_ALL_SCNS
-#endif
-#undef MR_INST
-    default: return hipErrorInvalidValue;
-  }
-}
-// clusters the scenario's step kernel keeps resident (0: unknown)
-static uint32_t step_capacity(const Dev& D, uint32_t scn, int device) {
-  switch (scn) {
-#define MR_INST(S) \
-  case S: return capacity_any<S>(D, device);
+// ---- one map from (scenario, servers, kernel family) to the kernel instance that runs it
+enum Family : uint32_t { F_STEP, F_POOL, F_TAPE };
+template <uint32_t S_, uint32_t NB_, Family F_>
+struct Inst { static constexpr uint32_t S = S_, NB = NB_, F = F_; };
+// scenarios this library holds instances of: all of the table's, or the few of a dev variant
+// (build.py scns=); a debug library may also lack the decision-tape kernels (build.build_guard)
 #ifdef MR_DEV_SCNS
-    MR_DEV_SCNS
+#define MR_BUILT_SCNS MR_DEV_SCNS
 #else
-    MR_ALL_SCNS
+#define MR_BUILT_SCNS MR_ALL_SCNS
 #endif
+#if MR_NO_TAPE
+constexpr bool k_has_tape = false;
+#else
+constexpr bool k_has_tape = true;
+#endif
+template <uint32_t S, uint32_t NB, class Fn>
+static bool visit_exact(uint32_t n, Family fam, Fn& fn) {
+  if (n != NB) return false;
+  if constexpr (has_pool(S, NB)) if (fam == F_POOL) return fn(Inst<S, NB, F_POOL>{}), true;
+  if constexpr (has_exact(S, NB)) if (fam == F_STEP) return fn(Inst<S, NB, F_STEP>{}), true;
+  return false;
+}
+// Calls fn(Inst<S, NB, F>{}) with the instance of scenario `scn` for n servers in family `fam`: the
+// exact-size one where it is built (mr_dev.h has_exact / has_pool), else for the step kernel the
+// 8-server one; tape kernels exist at 8 only. False, and no call, if the library holds none.
+template <class Fn>
+static bool visit_instance(uint32_t scn, uint32_t n, Family fam, Fn fn) {
+  switch (scn) {
+#define MR_INST(S)                                                                        \
+  case S:                                                                                 \
+    if constexpr (k_has_tape)                                                             \
+      if (fam == F_TAPE) return fn(Inst<S, MR_MAX_NODES, F_TAPE>{}), true;                \
+    if (fam == F_TAPE) return false;                                                      \
+    return visit_exact<S, 3>(n, fam, fn) || visit_exact<S, 5>(n, fam, fn) ||              \
+           visit_exact<S, 7>(n, fam, fn) ||                                               \
+           (fam == F_STEP && (fn(Inst<S, MR_MAX_NODES, F_STEP>{}), true));
+    MR_BUILT_SCNS
 #undef MR_INST
-    default: return 0;
+    default: return false;
   }
+}
+static Family family_of(const Dev& D) { return D.tape_mode ? F_TAPE : D.pool ? F_POOL : F_STEP; }
+// the kernel instance of scenario `scn` for this batch
+hipError_t launch_step(const Dev& D, uint32_t scn, uint32_t budget, hipStream_t s) {
+  hipError_t r = hipErrorInvalidValue;
+  visit_instance(scn, D.n, family_of(D), [&](auto i) {
+    using I = decltype(i);
+    if constexpr (I::F == F_TAPE) r = launch_step_tape_t<I::S, I::NB>(D, budget, s);
+    else if constexpr (I::F == F_POOL) r = launch_pool_t<I::S, I::NB>(D, budget, s);
+    else r = launch_step_t<I::S, I::NB>(D, budget, s);
+  });
+  return r;
+}
+// clusters the scenario's pool / step kernel keeps resident (0: unknown)
+static uint32_t step_capacity(const Dev& D, uint32_t scn, int device) {
+  uint32_t cap = 0;
+  visit_instance(scn, D.n, D.pool ? F_POOL : F_STEP, [&](auto i) {
+    using I = decltype(i);
+    if constexpr (I::F == F_POOL) cap = pool_capacity_t<I::S, I::NB>(device, D.M);
+    else cap = step_capacity_t<I::S, I::NB>(device, D.M);
+  });
+  return cap;
 }
 // the pool kernel serves this batch: an instance exists, the key rows fit (pool_max_slots), and the
 // environment does not turn it off (MR_POOL=0: the per-lane step kernel, for A/B runs)
 static bool use_pool(uint32_t scn, uint32_t n, uint32_t M) {
   if (const char* e = std::getenv("MR_POOL")) if (e[0] == '0') return false;
-  switch (scn) {
-#define MR_INST(S) \
-  case S: return has_pool(S, n) && M <= pool_max_slots(S, n);
-#ifdef MR_DEV_SCNS
-    MR_DEV_SCNS
-#else
-    MR_ALL_SCNS
-#endif
-#undef MR_INST
-    default: return false;
-  }
+  bool fits = false;
+  visit_instance(scn, n, F_POOL, [&](auto i) { fits = M <= pool_max_slots(i.S, i.NB); });
+  return fits;
 }
 hipError_t launch_reset(const Dev& D, hipStream_t s);
 hipError_t launch_reduce(const Dev& D, unsigned long long* out, uint64_t cluster_base,
@@ -113,28 +108,6 @@ int set_err(const std::string& s) {
     if (e_ != hipSuccess)                                                             \
       return set_err(std::string(#expr) + ": " + hipGetErrorString(e_));              \
   } while (0)
-
-const char* k_names[MR_SCN_COUNT_] = {
-    "", "initial_election_2a", "reelection_2a", "many_election_2a", "basic_agree_2b",
-    "fail_agree_2b", "fail_no_agree_2b", "concurrent_starts_2b", "rejoin_2b", "backup_2b",
-    "count_2b", "persist1_2c", "persist2_2c", "persist3_2c", "figure_8_2c",
-    "unreliable_agree_2c", "figure_8_unreliable_2c", "reliable_churn_2c",
-    "unreliable_churn_2c", "snapshot_basic_2d", "snapshot_install_2d",
-    "snapshot_install_unreliable_2d", "snapshot_install_crash_2d",
-    "snapshot_install_unreliable_crash_2d", "figure_8_unreliable_crash", "basic_3a",
-    "concurrent_3a", "unreliable_3a", "basic_4a", "multi_4a",
-    "many_partitions_one_client_3a", "many_partitions_many_clients_3a", "persist_one_client_3a",
-    "persist_concurrent_3a", "persist_concurrent_unreliable_3a", "persist_partition_3a",
-    "persist_partition_unreliable_3a", "unreliable_one_key_3a", "one_partition_3a",
-    "snapshot_rpc_3b", "snapshot_size_3b", "snapshot_recover_3b", "snapshot_recover_many_clients_3b",
-    "snapshot_unreliable_3b", "snapshot_unreliable_recover_3b",
-    "snapshot_unreliable_recover_concurrent_partition_3b",
-    "persist_partition_unreliable_linearizable_3a",
-    "snapshot_unreliable_recover_concurrent_partition_linearizable_3b"};
-// servers per test (tests.rs `let servers = ..`)
-const uint8_t k_nodes[MR_SCN_COUNT_] = {0, 3, 3, 7, 5, 3, 5, 3, 3, 5, 3, 3, 5, 3,
-                                        5, 5, 5, 5, 5, 3, 3, 3, 3, 3, 5, 5, 5, 5, 3, 3,
-                                        5, 5, 5, 5, 5, 5, 5, 3, 5, 3, 3, 5, 5, 5, 5, 5, 7, 7};
 
 constexpr size_t RED_N = CNT__N + 8 + 64 + 32 + 3;  // reduce_kernel output slots
 constexpr uint32_t STEP_LANES = 64;  // lanes per step-kernel block (one wave)
@@ -166,85 +139,38 @@ extern "C" {
 
 const char* mr_last_error(void) { return g_err.c_str(); }
 
-const char* mr_scenario_name(uint32_t s) { return (s > 0 && s < MR_SCN_COUNT_) ? k_names[s] : ""; }
+const char* mr_scenario_name(uint32_t s) {
+  switch (s) {
+#define MR_ROW_(id, sym, name, n, kind, slots, exact, pool) case id: return name;
+    MR_SCENARIO_TABLE(MR_ROW_)
+#undef MR_ROW_
+    default: return "";
+  }
+}
 
 uint32_t mr_scenario_from_name(const char* name) {
   if (!name) return 0;
   for (uint32_t i = 1; i < MR_SCN_COUNT_; i++)
-    if (std::strcmp(name, k_names[i]) == 0) return i;
+    if (std::strcmp(name, mr_scenario_name(i)) == 0) return i;
   return 0;
 }
 
 const char* mr_fail_message(uint32_t code) {
   switch (code) {
-    case MR_PASS: return "ok";
-    case MR_FAIL_ONE_LEADER_NONE: return "expected one leader, got none";
-    case MR_FAIL_MULTI_LEADER_TERM: return "term has (>1) leaders";
-    case MR_FAIL_TERM_DISAGREE: return "servers disagree on term";
-    case MR_FAIL_UNEXPECTED_LEADER: return "expected no leader, but claims to be leader";
-    case MR_FAIL_WAIT_TOO_FEW: return "only decided for index; wanted more";
-    case MR_FAIL_ONE_NO_AGREEMENT: return "one() failed to reach agreement";
-    case MR_FAIL_TIMEOUT_120S: return "test took longer than 120 seconds";
-    case MR_FAIL_APPLY_MISMATCH: return "commit index mismatch between servers";
-    case MR_FAIL_APPLY_OUT_OF_ORDER: return "server apply out of order";
-    case MR_FAIL_COMMIT_MISMATCH: return "committed values do not match";
-    case MR_FAIL_UNWRAP_NONE: return "called `Option::unwrap()` on a `None` value";
-    case MR_FAIL_LOG_SIZE: return "log size too large";
-    case MR_FAIL_BASIC_PRECOMMIT: return "some have committed before start()";
-    case MR_FAIL_BASIC_INDEX: return "got index but expected another";
-    case MR_FAIL_LEADER_REJECTED: return "leader rejected start";
-    case MR_FAIL_EXPECTED_INDEX2: return "expected index 2";
-    case MR_FAIL_NO_MAJORITY_COMMIT: return "committed but no majority";
-    case MR_FAIL_UNEXPECTED_INDEX: return "unexpected index";
-    case MR_FAIL_CMD_MISSING: return "cmd missing";
-    case MR_FAIL_TERM_CHANGED: return "term changed too often";
-    case MR_FAIL_RPC_INITIAL: return "too many or few RPCs to elect initial leader";
-    case MR_FAIL_START_FAILED: return "start failed";
-    case MR_FAIL_WRONG_VALUE: return "wrong value committed";
-    case MR_FAIL_RPC_TOO_MANY: return "too many RPCs for entries";
-    case MR_FAIL_RPC_IDLE: return "too many RPCs for 1 second of idleness";
-    case MR_FAIL_CHURN_VALUE: return "didn't find a value";
-    case MR_FAIL_KV_GET_WRONG: return "get wrong value";
-    case MR_FAIL_KV_MISSING: return "missing element in Append result";
-    case MR_FAIL_KV_APPEND_BAD: return "duplicate or wrong order element in Append result";
-    case MR_FAIL_CTRL_NGROUPS: return "assertion failed: c.groups.len() == groups.len()";
-    case MR_FAIL_CTRL_MISSING: return "missing group";
-    case MR_FAIL_CTRL_INVALID: return "shard -> invalid group";
-    case MR_FAIL_CTRL_IMBALANCED: return "imbalanced sharding";
-    case MR_FAIL_CTRL_SERVERS: return "wrong servers for gid";
-    case MR_FAIL_CTRL_HISTORY: return "historical query differs";
-    case MR_FAIL_CTRL_MOVE_NUM: return "Move should increase Tester.Num";
-    case MR_FAIL_CTRL_MOVE_WRONG: return "shard wrong group";
-    case MR_FAIL_CTRL_MINIMAL_JOIN: return "non-minimal transfer after Join()s";
-    case MR_FAIL_CTRL_MINIMAL_LEAVE: return "non-minimal transfer after Leave()s";
-    case MR_FAIL_CTRL_NO_LEADER: return "Leader not found";
-    case MR_FAIL_CTRL_SAME_CONFIG: return "config differs after leader shutdown";
-    case MR_FAIL_SAFETY_ELECTION: return "election safety: two leaders in one term";
-    case MR_FAIL_SAFETY_COMPLETENESS: return "leader completeness: new leader lacks a committed entry";
-    case MR_FAIL_KV_LOG_SIZE: return "logs were not trimmed";
-    case MR_FAIL_KV_SNAPSHOT_SIZE: return "snapshot too large";
-    case MR_FAIL_KV_MINORITY_PROGRESS: return "put/get in minority completed";
-    case MR_FAIL_KV_NO_COMPLETION: return "put/get did not complete";
-    case MR_FAIL_KV_CHECK: return "get(key) check failed";
-    case MR_FAIL_SAFETY_LOG_MATCHING: return "log matching: same index and term, different entries";
-    case MR_FAIL_TODO_APPLY: return "not yet implemented: apply command";
-    case MR_FAIL_TODO_RPC_RESULTS: return "not yet implemented: handle RPC results";
-    case MR_FAIL_KV_NOT_LINEARIZABLE: return "history is not linearizable";
-    case MR_FAIL_SIM_CAPACITY: return "simulator capacity exceeded";
-    case MR_FAIL_SIM_EVENT_LIMIT: return "simulator event limit exceeded";
-    case MR_FAIL_SIM_BAD_PROGRAM: return "scenario program error";
-    case MR_RUNNING: return "running";
+#define MR_ROW_(code, sym, msg) case code: return msg;
+    MR_FAIL_TABLE(MR_ROW_)
+#undef MR_ROW_
     default: return "unknown";
   }
 }
 
 int mr_cfg_init(mr_cfg* c, uint32_t scn) {
   if (!c) return set_err("null cfg");
-  if (scn == 0 || scn >= MR_SCN_COUNT_) return set_err("unknown scenario");
+  if (mr_scn_servers(scn) == 0) return set_err("unknown scenario");
   std::memset(c, 0, sizeof *c);
   c->abi_version = MR_ABI_VERSION;
   c->scenario = scn;
-  c->n_nodes = k_nodes[scn];
+  c->n_nodes = mr_scn_servers(scn);  // tests.rs `let servers = ..`
   c->seed_base = 1629626496ull;  // README.md:48
   c->n_clusters = 1;
   /* capacities sized from the oracle's maxima over 2000 seeds */
@@ -259,7 +185,7 @@ int mr_cfg_init(mr_cfg* c, uint32_t scn) {
   c->apply_cap = cap ? cap : (snap ? 1024 : 512);
   /* in-flight maxima over 64K / 1K seeds: 20 (figure_8), <= 45 (7 / 8 servers,
    * kvraft), 229 (20 clerks); a send past msg_slots fails the cluster (MR_FAIL_SIM_CAPACITY) */
-  c->msg_slots = mr_scn_wide_slots(scn) ? 256 : kv ? 64 : 32;
+  c->msg_slots = mr_scn_msg_slots(scn);
   c->ae_max = 16;
   c->hb_us = 50000;
   c->elect_lo_us = 150000;  // raft.rs:262
@@ -272,7 +198,7 @@ int mr_cfg_init(mr_cfg* c, uint32_t scn) {
 static int validate(const mr_cfg* c) {
   if (!c) return set_err("null cfg");
   if (c->abi_version != MR_ABI_VERSION) return set_err("abi_version mismatch");
-  if (c->scenario == 0 || c->scenario >= MR_SCN_COUNT_) return set_err("unknown scenario");
+  if (mr_scn_servers(c->scenario) == 0) return set_err("unknown scenario");
   if (c->n_nodes < 3 || c->n_nodes > MR_MAX_NODES) return set_err("n_nodes must be 3..8");
   if (c->n_clusters == 0 || c->n_clusters > (1ull << 31)) return set_err("bad n_clusters");
   if (c->log_cap < 16 || (c->log_cap & (c->log_cap - 1))) return set_err("log_cap: power of 2 >= 16");

@@ -4,6 +4,7 @@ points (no GPU needed) behave."""
 import ctypes as C
 import os
 import re
+import shutil
 import subprocess
 import tempfile
 
@@ -100,17 +101,121 @@ def test_bad_config_is_an_error_not_a_crash(L):
         sim.Batch(cfg=cfg)
 
 
-def test_build_instance_tables_match_the_kernels():
-    """build.py compiles the exact-size step-kernel instances mr_dev.h's has_exact() names (the
-    host dispatches to them): the scenarios' default server counts and the 7-server set agree."""
-    dev = open(os.path.join(ROOT, "madraft_amd", "csrc", "mr_dev.h")).read()
-    body = re.search(r"k_default_n\[\]\s*=\s*\{([^}]*)\}", dev).group(1)
-    assert [int(v) for v in body.replace("\n", " ").split(",")] == build.DEFAULT_N
-    lo, hi = re.search(r"has_nb7\(uint32_t s\) \{\s*return s >= (\w+) && s <= (\w+);", dev).groups()
-    hdr = open(HEADER).read()
-    ids = {m.group(1): int(m.group(2)) for m in re.finditer(r"(MR_SCN_\w+) = (\d+)", hdr)}
-    assert set(range(ids[lo], ids[hi] + 1)) == build.NB7_SCNS
-    assert ids["MR_SCN_FAIL_AGREE_2B"] == 5 and build.has_exact(5, 5)  # BASELINE config 2
+def test_fail_table_matches_library(L):
+    """Every verdict row of the header has a Python name and a message; other codes have none."""
+    body = open(HEADER).read().split("#define MR_FAIL_TABLE(X)", 1)[1].split("enum mr_fail", 1)[0]
+    rows = re.findall(r'^\s*X\((0x[0-9A-Fa-f]+|\d+), (\w+), "', body, re.M)
+    codes = {int(c, 0) for c, _ in rows}
+    assert len(codes) == len(rows) >= 57 and {0, 62, 0xFFFF} <= codes
+    assert codes == set(_abi.FAIL_NAMES)
+    for c, sym in rows:
+        assert _abi.FAIL_NAMES[int(c, 0)] in (sym, sym[len("FAIL_"):])
+        assert sim.fail_message(int(c, 0)) not in ("", "unknown"), sym
+    assert _abi.FAIL_NAMES[0] == "PASS" and _abi.FAIL_NAMES[0xFFFF] == "RUNNING"
+    for c in (set(range(64)) | {0xFFFE, 0x10000, 1 << 31}) - codes:
+        assert sim.fail_message(c) == "unknown", c
+
+
+def test_table_parser_rejects_a_row_it_cannot_read(tmp_path, monkeypatch):
+    bad = tmp_path / "bad.h"
+    bad.write_text('#define MR_FAIL_TABLE(X) \\\n  X(0, PASS, "ok") \\\n  X(1,FAIL_X, "x")\n')
+    monkeypatch.setattr(_abi, "HEADER", str(bad))
+    with pytest.raises(ValueError, match="FAIL_X"):
+        _abi._table("MR_FAIL_TABLE")
+
+
+def test_scenario_table_matches_library(L):
+    """Every row of the header's scenario table: the library's name, id and default config."""
+    assert [r.id for r in _abi.SCENARIO_ROWS] == list(range(1, len(_abi.SCENARIOS)))
+    for r in _abi.SCENARIO_ROWS:
+        assert L.mr_scenario_name(r.id).decode() == r.name
+        assert L.mr_scenario_from_name(r.name.encode()) == r.id
+        cfg = _abi.MrCfg()
+        assert L.mr_cfg_init(C.byref(cfg), r.id) == 0
+        assert (cfg.scenario, cfg.n_nodes, cfg.msg_slots) == (r.id, r.servers, r.slots), r.name
+    assert L.mr_scenario_name(len(_abi.SCENARIOS)).decode() == ""
+    assert L.mr_cfg_init(C.byref(_abi.MrCfg()), len(_abi.SCENARIOS)) != 0
+
+
+PREDICATES_SRC = """
+#include <cstdio>
+#include "{dev}"
+int main() {{
+  for (uint32_t s = 1; s < MR_SCN_COUNT_; s++)
+    for (uint32_t n = 3; n <= 8; n++)
+      std::printf("%u %u %d %d %u %d %d\\n", s, n, (int)mr::has_exact(s, n), (int)mr::has_pool(s, n),
+                  mr_scn_pool(s), mr_scn_wide_slots(s), mr_scn_is_lin15(s));
+  return 0;
+}}"""
+
+
+@pytest.fixture(scope="module")
+def predicates():
+    """mr_dev.h's instance predicates, evaluated by a host program: {(id, n): (has_exact,
+    has_pool, pool family, wide slots, lin15)} for every id and n = 3..8."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    inc = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "include")
+    with tempfile.TemporaryDirectory() as d:
+        src, exe = os.path.join(d, "p.cpp"), os.path.join(d, "p")
+        open(src, "w").write(PREDICATES_SRC.format(dev=os.path.join(ROOT, "madraft_amd", "csrc",
+                                                                    "mr_dev.h")))
+        subprocess.run(["g++", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", inc, "-o", exe, src],
+                       check=True)
+        out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
+    rows = [tuple(map(int, line.split())) for line in out.splitlines()]
+    return {(s, n): (bool(e), bool(p), fam, bool(w), bool(lin)) for s, n, e, p, fam, w, lin in rows}
+
+
+def unit_instances(units):
+    """(unit kind, id, NB) of every kernel instance the translation units `units` hold."""
+    inst = []
+    for src, name, flags in units:
+        if not src.endswith(".hip"):
+            continue
+        d = dict(f[2:].split("=", 1) for f in flags)
+        kind = ("tape" if d.get("MR_TAPE") == "1" else
+                {None: "step", "1": "pool", "2": "svcpool"}[d.get("MR_POOL")])
+        ids = [int(i) for i in re.findall(r"MR_INST\((\d+)\)", d["MR_SCN_LIST"])]
+        assert (d["MR_COMMON"] == "1") == (not ids) == (name == "common"), (name, flags)
+        inst += [(kind, i, int(d["MR_NB"]), d.get("MR_MW") == "4") for i in ids]
+    return inst
+
+
+@pytest.mark.parametrize("plan", ["full", "guard", "dev"])
+def test_build_plan_matches_the_kernels_predicates(predicates, plan):
+    """build.py compiles exactly the kernel instances mr_dev.h's has_exact() / has_pool() name,
+    which are the ones the host dispatches to: a difference is an undefined symbol when the
+    library loads, or a missing kernel at the first launch."""
+    scns, tape = {"full": (None, True), "guard": (build.GUARD_SCNS, False),
+                  "dev": ([16], True)}[plan]
+    ids = list(scns or build.SCN_IDS)
+    if plan == "full":
+        assert sorted({s for s, _ in predicates}) == ids == list(_abi.SCENARIO_ID.values())
+        assert [_abi.SCENARIOS[i] for i in ids if predicates[i, 8][4]] == _abi.LIN_TESTS
+    inst = unit_instances(build._units(os.path.join(ROOT, "madraft_amd", "csrc"), scns, tape))
+    assert len(set(i[:3] for i in inst)) == len(inst)  # no instance in two units
+    for kind, i, nb, wide in inst:
+        assert wide == predicates[i, nb][3], (kind, i, nb)  # 256-slot kernels: MR_MW=4 units
+    want = {("step", i, 8) for i in ids}
+    want |= {("tape", i, 8) for i in ids if tape}
+    for i in ids:
+        for n in range(3, 9):
+            exact, pool, fam = predicates[i, n][:3]
+            want |= {("step", i, n)} if exact else set()
+            want |= {({1: "pool", 2: "svcpool"}[fam], i, n)} if pool else set()
+            assert not pool or exact  # pool instances at exact sizes only
+            assert build.has_exact(i, n) == exact and build.has_pool(i, n) == pool
+    assert {i[:3] for i in inst} == want
+
+
+def test_pinned_exact_instances(predicates):
+    """The instances the BASELINE configs run on exist: config 2 (fail_agree_2b at 5 servers),
+    config 4 (the 2D tests at 7), each scenario's default count; none is "exact" at 8."""
+    assert _abi.SCENARIO_ID["fail_agree_2b"] == 5 and predicates[5, 5][0] and build.has_exact(5, 5)
+    for t in ("snapshot_basic_2d", "snapshot_install_2d", "snapshot_install_unreliable_2d",
+              "snapshot_install_crash_2d", "snapshot_install_unreliable_crash_2d"):
+        assert predicates[_abi.SCENARIO_ID[t], 7][0] and build.has_exact(_abi.SCENARIO_ID[t], 7)
     for i in build.SCN_IDS:
         assert build.has_exact(i, build.DEFAULT_N[i]) == (build.DEFAULT_N[i] < 8)
-        assert not build.has_exact(i, 8)
+        assert predicates[i, build.DEFAULT_N[i]][0] == (build.DEFAULT_N[i] < 8)
+        assert not build.has_exact(i, 8) and not predicates[i, 8][0]
