@@ -29,6 +29,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -40,8 +41,9 @@ extern "C" {
 #define MR_MAX_AE 32u
 
 /* ---- scenarios: one id per reference #[madsim::test] (src/raft/tests.rs) ----
- * The one place that describes a scenario; enum mr_scenario, the names, mr_cfg_init's defaults, the
- * kernel instances built and dispatched to and the Python mirror are generated from these rows:
+ * The one place that describes a scenario; enum mr_scenario, the names, the defaults of mr_cfg_init
+ * and of the oracle's mro_cfg_init (mr_cfg_defaults below), the kernel instances built and
+ * dispatched to and the Python mirror are generated from these rows:
  *   X(id, SYMBOL, "test name", servers, kind, slots, exact, pool)
  *   kind   RAFT, KV (kvraft generic_test and its variants) or CTRL (shard_ctrler)
  *   slots  default mr_cfg.msg_slots: 32, 64, or 256 (clerks keep more than 64 messages in flight)
@@ -155,6 +157,17 @@ MR_TABLE_FN_ int mr_scn_is_lin15(uint32_t s) {
 }
 /* scenarios whose clerks keep more than 64 messages in flight: 256 message slots */
 MR_TABLE_FN_ int mr_scn_wide_slots(uint32_t s) { return mr_scn_msg_slots(s) > 64u; }
+/* the figure_8 bodies, snap_common's five 2D tests (tests.rs:913-941), the churn tests */
+MR_TABLE_FN_ int mr_scn_is_fig8(uint32_t s) {
+  return s == MR_SCN_FIGURE_8_2C || s == MR_SCN_FIGURE_8_UNRELIABLE_2C ||
+         s == MR_SCN_FIGURE_8_UNRELIABLE_CRASH;
+}
+MR_TABLE_FN_ int mr_scn_is_snap2d(uint32_t s) {
+  return s >= MR_SCN_SNAPSHOT_BASIC_2D && s <= MR_SCN_SNAPSHOT_INSTALL_UNRELIABLE_CRASH_2D;
+}
+MR_TABLE_FN_ int mr_scn_is_churn(uint32_t s) {
+  return s == MR_SCN_RELIABLE_CHURN_2C || s == MR_SCN_UNRELIABLE_CHURN_2C;
+}
 /* default log / apply capacity of a kvraft scenario (no snapshots: every op stays in the log),
  * from the oracle's maxima: the bodies named here need more than 2048; 0 for any other id */
 MR_TABLE_FN_ uint32_t mr_kv_log_cap(uint32_t s) {
@@ -192,8 +205,8 @@ MR_TABLE_FN_ uint32_t mr_kv_log_cap(uint32_t s) {
 #define MR_F_BUG_NO_APPLY_CHECK 0x800u
 
 /* ---- verdicts: one code per tester panic site ----
- * X(code, SYMBOL, "message"): enum mr_fail { MR_<SYMBOL> = code }, mr_fail_message(code) and the
- * Python mirror's FAIL_NAMES come from these rows. The comments cite the panic and, where the
+ * X(code, SYMBOL, "message"): enum mr_fail { MR_<SYMBOL> = code }, mr_fail_message(code), the
+ * oracle's mro_fail_message and the Python mirror's FAIL_NAMES come from these rows. The comments cite the panic and, where the
  * message shortens it, its format string. */
 #define MR_FAIL_TABLE(X) \
   X(0, PASS, "ok") \
@@ -298,6 +311,44 @@ typedef struct mr_cfg {
   uint32_t reserved[3];
 } mr_cfg;
 
+/* The reference's defaults for scenario `scn` (mr_cfg_init and the oracle's mro_cfg_init are this);
+ * -1 and cfg untouched for an id without a row. */
+static inline int mr_cfg_defaults(mr_cfg* c, uint32_t scn) {
+  if (mr_scn_servers(scn) == 0) return -1;
+  memset(c, 0, sizeof *c);
+  c->abi_version = MR_ABI_VERSION;
+  c->scenario = scn;
+  c->n_nodes = mr_scn_servers(scn); /* tests.rs `let servers = ..` */
+  c->seed_base = 1629626496ull;     /* README.md:48 */
+  c->n_clusters = 1;
+  /* capacities sized from the oracle's maxima over 2000 seeds */
+  uint32_t cap = mr_scn_is_fig8(scn) ? 2048 : mr_scn_is_kv(scn) ? mr_kv_log_cap(scn)
+               : mr_scn_is_churn(scn) ? 4096 : scn == MR_SCN_UNRELIABLE_AGREE_2C ? 1024 : 0;
+  c->log_cap = cap ? cap : 256;
+  c->apply_cap = cap ? cap : (mr_scn_is_snap2d(scn) ? 1024 : 512);
+  /* in-flight maxima over 64K / 1K seeds: 20 (figure_8), <= 45 (7 / 8 servers,
+   * kvraft), 229 (20 clerks); a send past msg_slots fails the cluster (MR_FAIL_SIM_CAPACITY) */
+  c->msg_slots = mr_scn_msg_slots(scn);
+  c->ae_max = 16;
+  c->hb_us = 50000;
+  c->elect_lo_us = 150000; /* raft.rs:262 */
+  c->elect_hi_us = 300000;
+  c->max_events = 4u << 20;
+  c->trace_cap = 1u << 16;
+  return 0;
+}
+/* The capacity limits the kernels and the oracle share: what is wrong with cfg, or NULL. */
+static inline const char* mr_cfg_check_caps(const mr_cfg* c) {
+  if (c->n_nodes < 3 || c->n_nodes > MR_MAX_NODES) return "n_nodes must be 3..8";
+  if (c->log_cap < 16 || (c->log_cap & (c->log_cap - 1))) return "log_cap: power of 2 >= 16";
+  if (c->apply_cap < 16) return "apply_cap too small";
+  if (c->msg_slots < 1 || c->msg_slots > MR_MAX_MSG_SLOTS ||
+      (c->msg_slots > 64 && !mr_scn_wide_slots(c->scenario)))
+    return "msg_slots must be 1..64 (1..256 for snapshot_recover_many_clients_3b)";
+  if (c->ae_max < 1 || c->ae_max > MR_MAX_AE) return "ae_max must be 1..32";
+  return NULL;
+}
+
 /* Whole-batch counters (sums over clusters unless named max/first). */
 typedef struct mr_counters {
   uint64_t clusters, done, passed, failed;
@@ -332,6 +383,35 @@ typedef struct mr_counters {
   uint64_t coop_entries;    /* HIP path only: AppendEntries entries a receiver's wave wrote for it
                              * (the cooperative receive of the 7- / 8-server step kernels) */
 } mr_counters;
+
+/* ---- per-cluster counters: what the kernels keep per cluster (mr_dev.h x.cnt[]) ----
+ *   X(SYMBOL, field, reduction, who)
+ * CNT_<SYMBOL> indexes the cluster's counter, mr_counters.<field> is its reduction over the batch
+ * (SUM, or MAX: the MAX rows come last), and `who` says whether the oracle keeps it too (BOTH:
+ * mro_result.<field>) or only the HIP path does (HIP). The CNT_ enum, the reduce kernel's rule,
+ * mr_batch_counters, the oracle's sums and the Python key lists (dist.py, the tests) come from these
+ * rows; the struct above stays written out, because its field order is ABI. */
+#define MR_COUNTER_TABLE(X) \
+  X(EV_MSG, ev_msg, SUM, BOTH) \
+  X(EV_TIMER, ev_timer, SUM, BOTH) \
+  X(EV_TESTER, ev_tester, SUM, BOTH) \
+  X(DROP_CLOG, drop_clog, SUM, BOTH) \
+  X(DROP_LOSS, drop_loss, SUM, BOTH) \
+  X(DROP_OVERFLOW, drop_overflow, SUM, BOTH) \
+  X(DROP_DELIVER, drop_deliver, SUM, BOTH) \
+  X(DROP_STALE, drop_stale, SUM, BOTH) \
+  X(ELECTIONS, elections, SUM, BOTH) \
+  X(LEADERS, leaders_elected, SUM, BOTH) \
+  X(APPLIES, applies, SUM, BOTH) \
+  X(SNAPSHOTS, snapshots, SUM, BOTH) \
+  X(INSTALLS, installs, SUM, BOTH) \
+  X(SHIPPED, entries_shipped, SUM, BOTH) \
+  X(LOG_WRITES, log_writes, SUM, BOTH) \
+  X(MATERIALIZED, entries_materialized, SUM, HIP) \
+  X(COOP, coop_entries, SUM, HIP) \
+  X(MAX_INFLIGHT, max_inflight, MAX, BOTH) \
+  X(MAX_LOG, max_log, MAX, BOTH) \
+  X(MAX_INDEX, max_index, MAX, BOTH)
 
 typedef struct mr_run_stats {
   uint64_t launches;       /* step-kernel launches */

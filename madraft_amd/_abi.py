@@ -45,16 +45,18 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
                       "include", "madraft_sim.h")
 _ROW = re.compile(r'\s*X\((\w+), (\w+), "((?:[^"\\]|\\.)*)"'
                   r'(?:, (\d+), (\w+), (\d+), (0x[0-9A-Fa-f]+), (\w+))?\)')
+_COUNTER_ROW = re.compile(r'\s*X\(([A-Z_]+), ([a-z_]+), (SUM|MAX), (BOTH|HIP)\)')
 
 
-def _table(name):
+def _table(name, row=_ROW):
     """The rows of the header's X-macro `name`, fields as written: X(id, SYMBOL, "text"[, servers,
-    kind, slots, exact mask, pool]) up to the first line that does not continue."""
+    kind, slots, exact mask, pool]), or what `row` reads, up to the first line that does not
+    continue."""
     with open(HEADER) as f:
         lines = f.read().split(f"#define {name}(X) \\\n", 1)[1].split("\n")
     rows = []
     for line in lines:
-        m = _ROW.match(line)
+        m = row.match(line)
         if m:
             rows.append(m.groups())
         elif line.lstrip().startswith("X("):
@@ -87,6 +89,14 @@ GPU_UNSUPPORTED = set(UNSUPPORTED)
 # MR_FAIL_TABLE: verdict code -> symbol without its MR_ / MR_FAIL_ prefix
 FAIL_NAMES = {int(code, 0): sym[5:] if sym.startswith("FAIL_") else sym
               for code, sym, *_ in _table("MR_FAIL_TABLE")}
+
+# MR_COUNTER_TABLE: the per-cluster counters in CNT_ order (reduce: SUM / MAX over the batch; who:
+# BOTH = the oracle keeps it too, HIP = the HIP path only)
+Counter = collections.namedtuple("Counter", "symbol field reduce who")
+COUNTER_ROWS = [Counter(*r) for r in _table("MR_COUNTER_TABLE", _COUNTER_ROW)]
+# mr_counters fields that are no per-cluster counter but sums over the batch all the same
+BATCH_SUMS = ["clusters", "done", "passed", "failed", "events", "msgs_sent", "virt_time_us",
+              "kv_ops", "kv_checked", "kv_lin_checked"]
 
 
 class MrCfg(C.Structure):

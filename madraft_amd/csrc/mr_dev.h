@@ -27,12 +27,27 @@ enum : uint32_t { R_F = 0, R_C = 1, R_L = 2, R_DOWN = 3 };
 enum : uint32_t { M_RV_REQ = 1, M_RV_REP, M_AE_REQ, M_AE_REP, M_IS_REQ, M_IS_REP, M_KV_REQ, M_KV_REP };
 enum : uint32_t { ST_TESTER = 1, ST_ELECT = 2, ST_NET = 3 };
 
-// per-cluster u32 counters (part of cs32); the last three are maxima
+// per-cluster u32 counters (part of cs32): the rows of madraft_sim.h's MR_COUNTER_TABLE
 enum : uint32_t {
-  CNT_EV_MSG, CNT_EV_TIMER, CNT_EV_TESTER, CNT_DROP_CLOG, CNT_DROP_LOSS, CNT_DROP_OVERFLOW,
-  CNT_DROP_DELIVER, CNT_DROP_STALE, CNT_ELECTIONS, CNT_LEADERS, CNT_APPLIES, CNT_SNAPSHOTS,
-  CNT_INSTALLS, CNT_SHIPPED, CNT_LOG_WRITES, CNT_MATERIALIZED, CNT_COOP,
-  CNT_MAX_INFLIGHT, CNT_MAX_LOG, CNT_MAX_INDEX, CNT__N
+#define MR_ROW_(sym, field, red, who) CNT_##sym,
+  MR_COUNTER_TABLE(MR_ROW_)
+#undef MR_ROW_
+  CNT__N
+};
+// counter k reduces over clusters as a maximum, not a sum: the table's MAX rows, its tail
+enum : uint32_t { CNT_RED_SUM, CNT_RED_MAX };
+constexpr bool cnt_is_max(uint32_t k) { return k >= CNT_MAX_INFLIGHT; }
+#define MR_ROW_(sym, field, red, who) \
+  static_assert(cnt_is_max(CNT_##sym) == (CNT_RED_##red == CNT_RED_MAX), #sym ": MAX rows come last");
+MR_COUNTER_TABLE(MR_ROW_)
+#undef MR_ROW_
+// reduce_kernel's output vector: the CNT__N counters, then these (two unused slots after
+// RED_FIRST_FAIL; the histograms take 64, 16 and 16 slots)
+enum : uint32_t {
+  RED_EVENTS = CNT__N, RED_MSGS, RED_VTIME, RED_DONE, RED_PASSED, RED_FIRST_FAIL,
+  RED_FAIL_HIST = RED_FIRST_FAIL + 3, RED_COV_LEADERS = RED_FAIL_HIST + 64,
+  RED_COV_EVENTS = RED_COV_LEADERS + 16, RED_KV_OPS = RED_COV_EVENTS + 16, RED_KV_CHECKED,
+  RED_KV_LIN, RED_N
 };
 
 // tester coroutine frame (per cluster): program counter, script locals,

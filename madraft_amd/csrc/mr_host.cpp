@@ -109,7 +109,6 @@ int set_err(const std::string& s) {
       return set_err(std::string(#expr) + ": " + hipGetErrorString(e_));              \
   } while (0)
 
-constexpr size_t RED_N = CNT__N + 8 + 64 + 32 + 3;  // reduce_kernel output slots
 constexpr uint32_t STEP_LANES = 64;  // lanes per step-kernel block (one wave)
 }  // namespace
 
@@ -134,6 +133,29 @@ struct mr_batch {
   uint32_t kern = 0;         // kernel family of the launches since the reset: 1 pool, 2 step / tape
   std::chrono::steady_clock::time_point t_submit;
 };
+
+// traced cluster k's row of `rows` ([trace_clusters][trace_cap]): its records so far, at most cap
+template <class T>
+static int copy_trace_row(mr_batch* b, uint32_t k, const T* rows, T* out, size_t cap, size_t* n) {
+  uint32_t tn = 0;
+  HIPCHK(hipMemcpy(&tn, b->D.cs32 + CS_IDX(CS_TRACEN, k, b->D.C), 4, hipMemcpyDeviceToHost));
+  size_t m = tn < b->D.trace_cap ? tn : b->D.trace_cap;
+  if (m > cap) m = cap;
+  HIPCHK(hipMemcpy(out, rows + (size_t)k * b->D.trace_cap, m * sizeof(T), hipMemcpyDeviceToHost));
+  *n = m;
+  return 0;
+}
+
+// A C entry point whose host allocations may throw: an error code across the C ABI, never an
+// exception
+template <class Fn>
+static int no_throw(const char* name, Fn fn) {
+  try {
+    return fn();
+  } catch (const std::exception& e) {
+    return set_err(std::string(name) + ": " + e.what());
+  }
+}
 
 extern "C" {
 
@@ -166,47 +188,15 @@ const char* mr_fail_message(uint32_t code) {
 
 int mr_cfg_init(mr_cfg* c, uint32_t scn) {
   if (!c) return set_err("null cfg");
-  if (mr_scn_servers(scn) == 0) return set_err("unknown scenario");
-  std::memset(c, 0, sizeof *c);
-  c->abi_version = MR_ABI_VERSION;
-  c->scenario = scn;
-  c->n_nodes = mr_scn_servers(scn);  // tests.rs `let servers = ..`
-  c->seed_base = 1629626496ull;  // README.md:48
-  c->n_clusters = 1;
-  /* capacities sized from the oracle's maxima over 2000 seeds */
-  int fig8 = scn == MR_SCN_FIGURE_8_2C || scn == MR_SCN_FIGURE_8_UNRELIABLE_2C ||
-             scn == MR_SCN_FIGURE_8_UNRELIABLE_CRASH;
-  int snap = scn >= MR_SCN_SNAPSHOT_BASIC_2D && scn <= MR_SCN_SNAPSHOT_INSTALL_UNRELIABLE_CRASH_2D;
-  int kv = mr_scn_is_kv(scn);
-  int churn = scn == MR_SCN_RELIABLE_CHURN_2C || scn == MR_SCN_UNRELIABLE_CHURN_2C;
-  uint32_t cap = fig8 ? 2048 : kv ? mr_kv_log_cap(scn)
-               : churn ? 4096 : scn == MR_SCN_UNRELIABLE_AGREE_2C ? 1024 : 0;
-  c->log_cap = cap ? cap : 256;
-  c->apply_cap = cap ? cap : (snap ? 1024 : 512);
-  /* in-flight maxima over 64K / 1K seeds: 20 (figure_8), <= 45 (7 / 8 servers,
-   * kvraft), 229 (20 clerks); a send past msg_slots fails the cluster (MR_FAIL_SIM_CAPACITY) */
-  c->msg_slots = mr_scn_msg_slots(scn);
-  c->ae_max = 16;
-  c->hb_us = 50000;
-  c->elect_lo_us = 150000;  // raft.rs:262
-  c->elect_hi_us = 300000;
-  c->max_events = 4u << 20;
-  c->trace_cap = 1u << 16;
-  return 0;
+  return mr_cfg_defaults(c, scn) == 0 ? 0 : set_err("unknown scenario");
 }
 
 static int validate(const mr_cfg* c) {
   if (!c) return set_err("null cfg");
   if (c->abi_version != MR_ABI_VERSION) return set_err("abi_version mismatch");
   if (mr_scn_servers(c->scenario) == 0) return set_err("unknown scenario");
-  if (c->n_nodes < 3 || c->n_nodes > MR_MAX_NODES) return set_err("n_nodes must be 3..8");
+  if (const char* bad = mr_cfg_check_caps(c)) return set_err(bad);  // shared with the oracle
   if (c->n_clusters == 0 || c->n_clusters > (1ull << 31)) return set_err("bad n_clusters");
-  if (c->log_cap < 16 || (c->log_cap & (c->log_cap - 1))) return set_err("log_cap: power of 2 >= 16");
-  if (c->apply_cap < 16) return set_err("apply_cap too small");
-  if (c->msg_slots < 1 || c->msg_slots > MR_MAX_MSG_SLOTS ||
-      (c->msg_slots > 64 && !mr_scn_wide_slots(c->scenario)))
-    return set_err("msg_slots must be 1..64 (1..256 for snapshot_recover_many_clients_3b)");
-  if (c->ae_max < 1 || c->ae_max > MR_MAX_AE) return set_err("ae_max must be 1..32");
   if (c->elect_hi_us <= c->elect_lo_us || c->hb_us == 0) return set_err("bad timers");
   if (c->max_events == 0) return set_err("max_events must be > 0");
   if ((c->flags & MR_F_TRACE) && (c->trace_cap == 0 || c->trace_clusters > c->n_clusters))
@@ -247,8 +237,7 @@ static int mr_batch_create_impl(const mr_cfg* cfg, mr_batch** out) {
   D.trace_cap = cfg->trace_cap;
   D.scenario = scn;
   // loop counts of the test bodies (tests.rs): many_election 10, figure_8 1000, snap_common 30
-  uint32_t def_iters = scn == MR_SCN_MANY_ELECTION_2A ? 10 : (scn >= MR_SCN_SNAPSHOT_BASIC_2D &&
-                       scn <= MR_SCN_SNAPSHOT_INSTALL_UNRELIABLE_CRASH_2D) ? 30 : 1000;
+  uint32_t def_iters = scn == MR_SCN_MANY_ELECTION_2A ? 10 : mr_scn_is_snap2d(scn) ? 30 : 1000;
   D.iters = cfg->iters ? cfg->iters : def_iters;
   D.seed0 = cfg->seed_base + cfg->cluster_base;
   D.pool = !(cfg->flags & MR_F_RECORD) && use_pool(scn, (uint32_t)n, (uint32_t)M) ? 1u : 0u;
@@ -593,35 +582,27 @@ int mr_batch_counters(mr_batch* b, mr_counters* out) {
   if (!b || !out) return set_err("null argument");
   HIPCHK(hipSetDevice(b->cfg.device));
   std::vector<unsigned long long> h(RED_N, 0);
-  h[CNT__N + 5] = ~0ull;
+  h[RED_FIRST_FAIL] = ~0ull;
   HIPCHK(hipMemcpyAsync(b->red, h.data(), RED_N * 8, hipMemcpyHostToDevice, b->stream));
   HIPCHK(launch_reduce(b->D, b->red, b->cfg.cluster_base, b->stream));
   HIPCHK(hipMemcpyAsync(h.data(), b->red, RED_N * 8, hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   std::memset(out, 0, sizeof *out);
   out->clusters = b->D.C;
-  out->ev_msg = h[CNT_EV_MSG]; out->ev_timer = h[CNT_EV_TIMER]; out->ev_tester = h[CNT_EV_TESTER];
-  out->drop_clog = h[CNT_DROP_CLOG]; out->drop_loss = h[CNT_DROP_LOSS];
-  out->drop_overflow = h[CNT_DROP_OVERFLOW]; out->drop_deliver = h[CNT_DROP_DELIVER];
-  out->drop_stale = h[CNT_DROP_STALE]; out->elections = h[CNT_ELECTIONS];
-  out->leaders_elected = h[CNT_LEADERS]; out->applies = h[CNT_APPLIES];
-  out->snapshots = h[CNT_SNAPSHOTS]; out->installs = h[CNT_INSTALLS];
-  out->entries_shipped = h[CNT_SHIPPED]; out->max_inflight = h[CNT_MAX_INFLIGHT];
-  out->max_log = h[CNT_MAX_LOG]; out->max_index = h[CNT_MAX_INDEX];
-  out->events = h[CNT__N + 0]; out->msgs_sent = h[CNT__N + 1]; out->virt_time_us = h[CNT__N + 2];
-  out->done = h[CNT__N + 3]; out->passed = h[CNT__N + 4]; out->failed = out->done - out->passed;
-  out->first_fail_cluster = h[CNT__N + 5];
-  for (int i = 0; i < 64; i++) out->fail_hist[i] = h[CNT__N + 8 + i];
+#define MR_ROW_(sym, field, red, who) out->field = h[CNT_##sym];
+  MR_COUNTER_TABLE(MR_ROW_)
+#undef MR_ROW_
+  out->events = h[RED_EVENTS]; out->msgs_sent = h[RED_MSGS]; out->virt_time_us = h[RED_VTIME];
+  out->done = h[RED_DONE]; out->passed = h[RED_PASSED]; out->failed = out->done - out->passed;
+  out->first_fail_cluster = h[RED_FIRST_FAIL];
+  for (int i = 0; i < 64; i++) out->fail_hist[i] = h[RED_FAIL_HIST + i];
   for (int i = 0; i < 16; i++) {
-    out->cov_leaders[i] = h[CNT__N + 72 + i];
-    out->cov_events[i] = h[CNT__N + 88 + i];
+    out->cov_leaders[i] = h[RED_COV_LEADERS + i];
+    out->cov_events[i] = h[RED_COV_EVENTS + i];
   }
-  out->kv_ops = h[CNT__N + 104];
-  out->kv_checked = h[CNT__N + 105];
-  out->kv_lin_checked = h[CNT__N + 106];
-  out->log_writes = h[CNT_LOG_WRITES];
-  out->entries_materialized = h[CNT_MATERIALIZED];
-  out->coop_entries = h[CNT_COOP];
+  out->kv_ops = h[RED_KV_OPS];
+  out->kv_checked = h[RED_KV_CHECKED];
+  out->kv_lin_checked = h[RED_KV_LIN];
   out->first_fail_code = 0;
   if (out->first_fail_cluster != ~0ull) {
     uint32_t code = 0;
@@ -636,14 +617,7 @@ int mr_trace_get(mr_batch* b, uint32_t k, mr_event* out, size_t cap, size_t* n) 
   if (!b || !out || !n) return set_err("null argument");
   if (k >= b->D.trace_clusters) return set_err("cluster not traced");
   HIPCHK(hipSetDevice(b->cfg.device));
-  uint32_t tn = 0;
-  HIPCHK(hipMemcpy(&tn, b->D.cs32 + CS_IDX(CS_TRACEN, k, b->D.C), 4, hipMemcpyDeviceToHost));
-  size_t m = tn < b->D.trace_cap ? tn : b->D.trace_cap;
-  if (m > cap) m = cap;
-  HIPCHK(hipMemcpy(out, b->D.trace + (size_t)k * b->D.trace_cap, m * sizeof(mr_event),
-                   hipMemcpyDeviceToHost));
-  *n = m;
-  return 0;
+  return copy_trace_row(b, k, b->D.trace, out, cap, n);
 }
 
 int mr_trace_digests(mr_batch* b, uint32_t k, uint64_t* out, size_t cap, size_t* n) {
@@ -651,14 +625,7 @@ int mr_trace_digests(mr_batch* b, uint32_t k, uint64_t* out, size_t cap, size_t*
   if (k >= b->D.trace_clusters) return set_err("cluster not traced");
   HIPCHK(hipSetDevice(b->cfg.device));
   HIPCHK(hipStreamSynchronize(b->stream));
-  uint32_t tn = 0;
-  HIPCHK(hipMemcpy(&tn, b->D.cs32 + CS_IDX(CS_TRACEN, k, b->D.C), 4, hipMemcpyDeviceToHost));
-  size_t m = tn < b->D.trace_cap ? tn : b->D.trace_cap;
-  if (m > cap) m = cap;
-  HIPCHK(hipMemcpy(out, b->D.tdig + (size_t)k * b->D.trace_cap, m * sizeof(uint64_t),
-                   hipMemcpyDeviceToHost));
-  *n = m;
-  return 0;
+  return copy_trace_row(b, k, b->D.tdig, out, cap, n);
 }
 
 int mr_trace_applies(mr_batch* b, uint32_t k, uint64_t* out, size_t cap, size_t* n) {
@@ -751,11 +718,7 @@ int mr_batch_set_decisions(mr_batch* b, const mr_decision* d, size_t n) {
   HIPCHK(hipSetDevice(b->cfg.device));
   HIPCHK(hipStreamSynchronize(b->stream));
   if (!n) { drop_decisions(b); return 0; }
-  try {  // host staging may not fit: an error code across the C ABI, never an exception
-    return set_decisions_impl(b, d, n);
-  } catch (const std::bad_alloc&) {
-    return set_err("decision table: host allocation failed");
-  }
+  return no_throw("decision table", [&] { return set_decisions_impl(b, d, n); });  // host staging
 }
 
 static int mr_batch_get_decisions_impl(mr_batch* b, uint32_t k, mr_decision* out, size_t cap, size_t* n) {
@@ -843,36 +806,23 @@ void mr_batch_destroy(mr_batch* b) {
 }
 
 int mr_batch_create(const mr_cfg* cfg, mr_batch** out) {
-  try {  // host allocations: an error code across the C ABI, never an exception
-    return mr_batch_create_impl(cfg, out);
-  } catch (const std::exception& e) {
-    return set_err(std::string("mr_batch_create: ") + e.what());
-  }
+  return no_throw("mr_batch_create", [&] { return mr_batch_create_impl(cfg, out); });
 }
 
 int mr_batch_verdicts(mr_batch* b, uint16_t* code, uint32_t* time_us, uint64_t* digest) {
-  try {  // host allocations: an error code across the C ABI, never an exception
-    return mr_batch_verdicts_impl(b, code, time_us, digest);
-  } catch (const std::exception& e) {
-    return set_err(std::string("mr_batch_verdicts: ") + e.what());
-  }
+  return no_throw("mr_batch_verdicts", [&] { return mr_batch_verdicts_impl(b, code, time_us, digest); });
 }
 
 int mr_batch_get_decisions(mr_batch* b, uint32_t k, mr_decision* out, size_t cap, size_t* n) {
-  try {  // host allocations: an error code across the C ABI, never an exception
-    return mr_batch_get_decisions_impl(b, k, out, cap, n);
-  } catch (const std::exception& e) {
-    return set_err(std::string("mr_batch_get_decisions: ") + e.what());
-  }
+  return no_throw("mr_batch_get_decisions",
+                  [&] { return mr_batch_get_decisions_impl(b, k, out, cap, n); });
 }
 
 int mr_replay(const mr_cfg* cfg, const mr_decision* d, size_t n, mr_event* out, size_t cap,
               size_t* n_out, uint16_t* code, uint32_t* time_us, uint64_t* misses) {
-  try {  // host allocations: an error code across the C ABI, never an exception
+  return no_throw("mr_replay", [&] {
     return mr_replay_impl(cfg, d, n, out, cap, n_out, code, time_us, misses);
-  } catch (const std::exception& e) {
-    return set_err(std::string("mr_replay: ") + e.what());
-  }
+  });
 }
 
 }  // extern "C"

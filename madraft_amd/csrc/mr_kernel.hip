@@ -2261,49 +2261,48 @@ __global__ void __launch_bounds__(256) reset_kernel(Dev D) {
 }
 
 // counters_reduce: per-GPU sums / maxima / verdict histogram / first failing
-// cluster; out[] layout documented in mr_host.cpp (RED_*)
+// cluster; out[] is laid out by mr_dev.h's CNT_* and RED_*
 __global__ void __launch_bounds__(256) reduce_kernel(Dev D, unsigned long long* out,
                                                     uint64_t cluster_base) {
-  constexpr uint32_t RN = CNT__N + 8 + 64 + 32 + 3;  // counters, scalars, verdicts, coverage, kv
-  __shared__ unsigned long long acc[RN];
-  for (uint32_t i = threadIdx.x; i < RN; i += blockDim.x) acc[i] = 0;
+  __shared__ unsigned long long acc[RED_N];
+  for (uint32_t i = threadIdx.x; i < RED_N; i += blockDim.x) acc[i] = 0;
   __syncthreads();
   X x;
   x.c = blockIdx.x * blockDim.x + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x < CNT__N) {  // the pool kernels' workgroup sums
     const unsigned long long v = D.pcnt[threadIdx.x];
     if (v) {
-      if (threadIdx.x >= CNT_MAX_INFLIGHT) atomicMax(&acc[threadIdx.x], v);
+      if (cnt_is_max(threadIdx.x)) atomicMax(&acc[threadIdx.x], v);
       else atomicAdd(&acc[threadIdx.x], v);
     }
   }
   if (x.c < D.C) {
     for (uint32_t k = 0; k < CNT__N; k++) {
       unsigned long long v = CS(CS_CNT + k);
-      if (k >= CNT_MAX_INFLIGHT) atomicMax(&acc[k], v);
+      if (cnt_is_max(k)) atomicMax(&acc[k], v);
       else atomicAdd(&acc[k], v);
     }
     uint32_t code = CS(CS_CODE);
-    atomicAdd(&acc[CNT__N + 0], (unsigned long long)CS(CS_EVENTS));
-    atomicAdd(&acc[CNT__N + 1], (unsigned long long)CS(CS_MSGS));
-    atomicAdd(&acc[CNT__N + 2], (unsigned long long)CS(CS_VTIME));
-    atomicAdd(&acc[CNT__N + 3], code != RUN ? 1ull : 0ull);
-    atomicAdd(&acc[CNT__N + 4], code == MR_PASS ? 1ull : 0ull);
-    if (code != RUN) atomicAdd(&acc[CNT__N + 8 + (code < 63 ? code : 63)], 1ull);
+    atomicAdd(&acc[RED_EVENTS], (unsigned long long)CS(CS_EVENTS));
+    atomicAdd(&acc[RED_MSGS], (unsigned long long)CS(CS_MSGS));
+    atomicAdd(&acc[RED_VTIME], (unsigned long long)CS(CS_VTIME));
+    atomicAdd(&acc[RED_DONE], code != RUN ? 1ull : 0ull);
+    atomicAdd(&acc[RED_PASSED], code == MR_PASS ? 1ull : 0ull);
+    if (code != RUN) atomicAdd(&acc[RED_FAIL_HIST + (code < 63 ? code : 63)], 1ull);
     auto bucket = [](uint32_t v) { return v == 0 ? 0u : min(15u, 32u - (uint32_t)__builtin_clz(v)); };
-    atomicAdd(&acc[CNT__N + 72 + bucket(CS(CS_CNT + CNT_LEADERS))], 1ull);
-    atomicAdd(&acc[CNT__N + 88 + bucket(CS(CS_EVENTS))], 1ull);
-    atomicAdd(&acc[CNT__N + 104], (unsigned long long)CS(CS_KV_OPS));
-    atomicAdd(&acc[CNT__N + 105], (unsigned long long)CS(CS_KV_CHECKED));
-    atomicAdd(&acc[CNT__N + 106], (unsigned long long)CS(CS_KV_LIN));
+    atomicAdd(&acc[RED_COV_LEADERS + bucket(CS(CS_CNT + CNT_LEADERS))], 1ull);
+    atomicAdd(&acc[RED_COV_EVENTS + bucket(CS(CS_EVENTS))], 1ull);
+    atomicAdd(&acc[RED_KV_OPS], (unsigned long long)CS(CS_KV_OPS));
+    atomicAdd(&acc[RED_KV_CHECKED], (unsigned long long)CS(CS_KV_CHECKED));
+    atomicAdd(&acc[RED_KV_LIN], (unsigned long long)CS(CS_KV_LIN));
     if (code != RUN && code != MR_PASS)
-      atomicMin(&out[CNT__N + 5], (unsigned long long)(cluster_base + x.c));
+      atomicMin(&out[RED_FIRST_FAIL], (unsigned long long)(cluster_base + x.c));
   }
   __syncthreads();
-  for (uint32_t i = threadIdx.x; i < RN; i += blockDim.x) {
-    if (i == CNT__N + 5 || i == CNT__N + 6 || i == CNT__N + 7) continue;
+  for (uint32_t i = threadIdx.x; i < RED_N; i += blockDim.x) {
+    if (i == RED_FIRST_FAIL || i == RED_FIRST_FAIL + 1 || i == RED_FIRST_FAIL + 2) continue;
     if (acc[i] == 0) continue;
-    if (i >= CNT_MAX_INFLIGHT && i < CNT__N) atomicMax(&out[i], acc[i]);
+    if (cnt_is_max(i) && i < CNT__N) atomicMax(&out[i], acc[i]);
     else atomicAdd(&out[i], acc[i]);
   }
 }

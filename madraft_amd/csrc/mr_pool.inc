@@ -567,12 +567,12 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
 #pragma unroll
   for (uint32_t k = 0; k < CNT__N; k++) {
     if (k == CNT_LEADERS || k == CNT_MAX_INDEX || x.cnt[k] == 0u) continue;
-    if (k >= CNT_MAX_INFLIGHT) atomicMax(&red[k], (unsigned long long)x.cnt[k]);
+    if (cnt_is_max(k)) atomicMax(&red[k], (unsigned long long)x.cnt[k]);
     else atomicAdd(&red[k], (unsigned long long)x.cnt[k]);
   }
   __syncthreads();
   if (tid < CNT__N && red[tid]) {
-    if (tid >= CNT_MAX_INFLIGHT) atomicMax(&D.pcnt[tid], red[tid]);
+    if (cnt_is_max(tid)) atomicMax(&D.pcnt[tid], red[tid]);
     else atomicAdd(&D.pcnt[tid], red[tid]);
   }
 }

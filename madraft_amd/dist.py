@@ -12,14 +12,10 @@ op. With backend "nccl" it is RCCL over xGMI. Tests run the same code with gloo 
 import torch
 import torch.distributed as dist
 
-from ._abi import FAIL_NAMES
+from ._abi import BATCH_SUMS, COUNTER_ROWS, FAIL_NAMES
 
-SUM_KEYS = ["clusters", "done", "passed", "failed", "events", "ev_msg", "ev_timer", "ev_tester",
-            "msgs_sent", "drop_clog", "drop_loss", "drop_overflow", "drop_deliver", "drop_stale",
-            "elections", "leaders_elected", "applies", "snapshots", "installs",
-            "entries_shipped", "virt_time_us", "kv_ops", "kv_checked", "log_writes",
-            "entries_materialized", "kv_lin_checked", "coop_entries"]
-MAX_KEYS = ["max_inflight", "max_log", "max_index"]
+SUM_KEYS = BATCH_SUMS + [r.field for r in COUNTER_ROWS if r.reduce == "SUM"]
+MAX_KEYS = [r.field for r in COUNTER_ROWS if r.reduce == "MAX"]
 COV_KEYS = ["cov_leaders", "cov_events"]
 NO_FAIL = (1 << 63) - 1
 

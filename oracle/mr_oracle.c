@@ -2533,12 +2533,7 @@ static int run_scenario(OSim* s) {
 static int sim_alloc(OSim* s, const mr_cfg* cfg) {
   memset(s, 0, sizeof *s);
   s->cfg = *cfg;
-  if (cfg->n_nodes < 3 || cfg->n_nodes > MR_MAX_NODES) return -1;
-  if (cfg->log_cap < 16 || (cfg->log_cap & (cfg->log_cap - 1))) return -1;
-  if (cfg->msg_slots < 1 || cfg->msg_slots > MR_MAX_MSG_SLOTS) return -1;
-  if (cfg->msg_slots > 64 && !mr_scn_wide_slots(cfg->scenario)) return -1;
-  if (cfg->ae_max < 1 || cfg->ae_max > MR_MAX_AE) return -1;
-  if (cfg->apply_cap < 16) return -1;
+  if (mr_cfg_check_caps(cfg)) return -1;
   for (uint32_t i = 0; i < cfg->n_nodes; i++) {
     s->nd[i].lterm = (uint32_t*)malloc(cfg->log_cap * sizeof(uint32_t));
     s->nd[i].lval = (uint64_t*)malloc(cfg->log_cap * sizeof(uint64_t));
@@ -2678,17 +2673,16 @@ int mro_run_cluster_kv(const mr_cfg* cfg, uint64_t cluster, mro_result* out, mr_
   return 0;
 }
 
+/* the batch's sums / maxima: the rows of MR_COUNTER_TABLE the oracle keeps, and the cluster scalars */
 static void acc(mro_result* a, const mro_result* b) {
-  a->events += b->events; a->ev_msg += b->ev_msg; a->ev_timer += b->ev_timer;
-  a->ev_tester += b->ev_tester; a->msgs_sent += b->msgs_sent; a->drop_clog += b->drop_clog;
-  a->drop_loss += b->drop_loss; a->drop_overflow += b->drop_overflow;
-  a->drop_deliver += b->drop_deliver; a->drop_stale += b->drop_stale;
-  a->elections += b->elections; a->leaders_elected += b->leaders_elected;
-  a->applies += b->applies; a->snapshots += b->snapshots; a->installs += b->installs;
-  a->entries_shipped += b->entries_shipped; a->log_writes += b->log_writes;
-  if (b->max_inflight > a->max_inflight) a->max_inflight = b->max_inflight;
-  if (b->max_log > a->max_log) a->max_log = b->max_log;
-  if (b->max_index > a->max_index) a->max_index = b->max_index;
+#define ACC_SUM(f) a->f += b->f;
+#define ACC_MAX(f) if (b->f > a->f) a->f = b->f;
+#define ACC_BOTH(red, f) ACC_##red(f)
+#define ACC_HIP(red, f)
+#define MR_ROW_(sym, field, red, who) ACC_##who(red, field)
+  MR_COUNTER_TABLE(MR_ROW_)
+#undef MR_ROW_
+  a->events += b->events; a->msgs_sent += b->msgs_sent;
   a->kv_ops += b->kv_ops; a->kv_checked += b->kv_checked; a->kv_lin_checked += b->kv_lin_checked;
 }
 
@@ -2710,93 +2704,22 @@ int mro_run_batch(const mr_cfg* cfg, uint64_t first, uint64_t count, uint16_t* c
 }
 
 /* ------------------------------------------------------------------ */
-/* names / defaults (mirrors mr_cfg_init of the product ABI)           */
+/* names / defaults / messages: the tables of madraft_sim.h            */
 /* ------------------------------------------------------------------ */
-static const char* k_names[MR_SCN_COUNT_] = {
-    "", "initial_election_2a", "reelection_2a", "many_election_2a", "basic_agree_2b",
-    "fail_agree_2b", "fail_no_agree_2b", "concurrent_starts_2b", "rejoin_2b", "backup_2b",
-    "count_2b", "persist1_2c", "persist2_2c", "persist3_2c", "figure_8_2c",
-    "unreliable_agree_2c", "figure_8_unreliable_2c", "reliable_churn_2c",
-    "unreliable_churn_2c", "snapshot_basic_2d", "snapshot_install_2d",
-    "snapshot_install_unreliable_2d", "snapshot_install_crash_2d",
-    "snapshot_install_unreliable_crash_2d", "figure_8_unreliable_crash", "basic_3a",
-    "concurrent_3a", "unreliable_3a", "basic_4a", "multi_4a",
-    "many_partitions_one_client_3a", "many_partitions_many_clients_3a", "persist_one_client_3a",
-    "persist_concurrent_3a", "persist_concurrent_unreliable_3a", "persist_partition_3a",
-    "persist_partition_unreliable_3a", "unreliable_one_key_3a", "one_partition_3a",
-    "snapshot_rpc_3b", "snapshot_size_3b", "snapshot_recover_3b", "snapshot_recover_many_clients_3b",
-    "snapshot_unreliable_3b", "snapshot_unreliable_recover_3b",
-    "snapshot_unreliable_recover_concurrent_partition_3b",
-    "persist_partition_unreliable_linearizable_3a",
-    "snapshot_unreliable_recover_concurrent_partition_linearizable_3b"};
-
 uint32_t mro_scenario_from_name(const char* name) {
-  for (uint32_t i = 1; i < MR_SCN_COUNT_; i++)
-    if (strcmp(name, k_names[i]) == 0) return i;
+#define MR_ROW_(id, sym, nm, n, kind, slots, exact, pool) if (strcmp(name, nm) == 0) return id;
+  MR_SCENARIO_TABLE(MR_ROW_)
+#undef MR_ROW_
   return 0;
 }
 
-int mro_cfg_init(mr_cfg* c, uint32_t scn) {
-  static const uint8_t k_n[MR_SCN_COUNT_] = {0, 3, 3, 7, 5, 3, 5, 3, 3, 5, 3, 3, 5, 3,
-                                             5, 5, 5, 5, 5, 3, 3, 3, 3, 3, 5, 5, 5, 5, 3, 3,
-                                             5, 5, 5, 5, 5, 5, 5, 3, 5, 3, 3, 5, 5, 5, 5, 5, 7, 7};
-  if (scn == 0 || scn >= MR_SCN_COUNT_) return -1;
-  memset(c, 0, sizeof *c);
-  c->abi_version = MR_ABI_VERSION;
-  c->scenario = scn;
-  c->n_nodes = k_n[scn];
-  c->seed_base = 1629626496ull; /* README.md:48 */
-  c->n_clusters = 1;
-  /* capacities sized from the oracle's maxima over 2000 seeds */
-  int fig8 = scn == MR_SCN_FIGURE_8_2C || scn == MR_SCN_FIGURE_8_UNRELIABLE_2C ||
-             scn == MR_SCN_FIGURE_8_UNRELIABLE_CRASH;
-  int snap = scn >= MR_SCN_SNAPSHOT_BASIC_2D && scn <= MR_SCN_SNAPSHOT_INSTALL_UNRELIABLE_CRASH_2D;
-  int kv = mr_scn_is_kv(scn);
-  int churn = scn == MR_SCN_RELIABLE_CHURN_2C || scn == MR_SCN_UNRELIABLE_CHURN_2C;
-  uint32_t cap = fig8 ? 2048 : kv ? mr_kv_log_cap(scn)
-               : churn ? 4096 : scn == MR_SCN_UNRELIABLE_AGREE_2C ? 1024 : 0;
-  c->log_cap = cap ? cap : 256;
-  c->apply_cap = cap ? cap : (snap ? 1024 : 512);
-  c->msg_slots = mr_scn_wide_slots(scn) ? 256 : kv ? 64 : 32;
-  c->ae_max = 16;
-  c->hb_us = 50000;
-  c->elect_lo_us = 150000;
-  c->elect_hi_us = 300000;
-  c->max_events = 4u << 20;
-  c->trace_cap = 1u << 16;
-  return 0;
-}
+int mro_cfg_init(mr_cfg* c, uint32_t scn) { return mr_cfg_defaults(c, scn); }
 
 const char* mro_fail_message(uint32_t code) {
   switch (code) {
-    case MR_PASS: return "ok";
-    case MR_FAIL_ONE_LEADER_NONE: return "expected one leader, got none";
-    case MR_FAIL_MULTI_LEADER_TERM: return "term has (>1) leaders";
-    case MR_FAIL_TERM_DISAGREE: return "servers disagree on term";
-    case MR_FAIL_UNEXPECTED_LEADER: return "expected no leader, but claims to be leader";
-    case MR_FAIL_WAIT_TOO_FEW: return "only decided for index; wanted more";
-    case MR_FAIL_ONE_NO_AGREEMENT: return "one() failed to reach agreement";
-    case MR_FAIL_TIMEOUT_120S: return "test took longer than 120 seconds";
-    case MR_FAIL_APPLY_MISMATCH: return "commit index mismatch between servers";
-    case MR_FAIL_APPLY_OUT_OF_ORDER: return "server apply out of order";
-    case MR_FAIL_UNWRAP_NONE: return "called `Option::unwrap()` on a `None` value";
-    case MR_FAIL_LOG_SIZE: return "log size too large";
-    case MR_FAIL_KV_GET_WRONG: return "get wrong value";
-    case MR_FAIL_KV_MISSING: return "missing element in Append result";
-    case MR_FAIL_KV_APPEND_BAD: return "duplicate or wrong order element in Append result";
-    case MR_FAIL_SAFETY_ELECTION: return "election safety: two leaders in one term";
-    case MR_FAIL_SAFETY_COMPLETENESS: return "leader completeness: new leader lacks a committed entry";
-    case MR_FAIL_KV_LOG_SIZE: return "logs were not trimmed";
-    case MR_FAIL_KV_SNAPSHOT_SIZE: return "snapshot too large";
-    case MR_FAIL_KV_MINORITY_PROGRESS: return "put/get in minority completed";
-    case MR_FAIL_KV_NO_COMPLETION: return "put/get did not complete";
-    case MR_FAIL_KV_CHECK: return "get(key) check failed";
-    case MR_FAIL_SAFETY_LOG_MATCHING: return "log matching: same index and term, different entries";
-    case MR_FAIL_TODO_APPLY: return "not yet implemented: apply command";
-    case MR_FAIL_TODO_RPC_RESULTS: return "not yet implemented: handle RPC results";
-    case MR_FAIL_KV_NOT_LINEARIZABLE: return "history is not linearizable";
-    case MR_FAIL_SIM_CAPACITY: return "simulator capacity exceeded";
-    case MR_FAIL_SIM_EVENT_LIMIT: return "simulator event limit exceeded";
-    default: return "scenario assertion failed";
+#define MR_ROW_(code, sym, msg) case code: return msg;
+    MR_FAIL_TABLE(MR_ROW_)
+#undef MR_ROW_
+    default: return "unknown";
   }
 }

@@ -8,10 +8,15 @@ import os
 
 import numpy as np
 
-from madraft_amd._abi import DECISION_DTYPE, EVENT_DTYPE, MrCfg
+from madraft_amd._abi import COUNTER_ROWS, DECISION_DTYPE, EVENT_DTYPE, MrCfg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "oracle", "_build", "libmr_oracle.so")
+
+# the counters of a batch the oracle keeps (mro_run_batch's sums / maxima), which the parity tests
+# compare: the rows of the header's counter table it shares with the HIP path, and the batch scalars
+COUNTER_KEYS = [r.field for r in COUNTER_ROWS if r.who == "BOTH"] + \
+    ["events", "msgs_sent", "kv_ops", "kv_checked", "kv_lin_checked"]
 
 
 class MroResult(C.Structure):
@@ -24,6 +29,11 @@ class MroResult(C.Structure):
 
     def to_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+# mro_result's field order is typed out above as in oracle/mr_oracle.h (the order is its layout);
+# which counters it holds is the table's to say
+assert {n for n, _ in MroResult._fields_[3:]} == set(COUNTER_KEYS)
 
 
 class Oracle:

@@ -11,6 +11,8 @@ import tempfile
 import pytest
 
 from madraft_amd import _abi, build, sim
+from madraft_amd import dist as mdist
+from tests import oracle_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "madraft_sim.h")
@@ -38,14 +40,37 @@ def test_exports_every_header_symbol(L):
         assert hasattr(L, n)
 
 
+# the key lists as they were typed out before the counter table (include/madraft_sim.h) named them
+PINNED_SUM_KEYS = ["clusters", "done", "passed", "failed", "events", "ev_msg", "ev_timer",
+                   "ev_tester", "msgs_sent", "drop_clog", "drop_loss", "drop_overflow",
+                   "drop_deliver", "drop_stale", "elections", "leaders_elected", "applies",
+                   "snapshots", "installs", "entries_shipped", "virt_time_us", "kv_ops",
+                   "kv_checked", "log_writes", "entries_materialized", "kv_lin_checked",
+                   "coop_entries"]
+PINNED_MAX_KEYS = ["max_inflight", "max_log", "max_index"]
+PINNED_PARITY_KEYS = ["events", "ev_msg", "ev_timer", "ev_tester", "msgs_sent", "drop_clog",
+                      "drop_loss", "drop_overflow", "drop_deliver", "drop_stale", "elections",
+                      "leaders_elected", "applies", "snapshots", "installs", "entries_shipped",
+                      "max_inflight", "max_log", "max_index", "kv_ops", "kv_checked", "log_writes",
+                      "kv_lin_checked"]
+
+
 def test_struct_layout_matches_c():
+    """sizeof / offsetof as the C compiler sees them against the ctypes mirrors, every counter-table
+    field of mr_counters and every counter of the oracle's mro_result among them."""
+    cnt = [r.field for r in _abi.COUNTER_ROWS]
+    assert cnt and set(cnt) <= {n for n, _ in _abi.MrCounters._fields_}
+    offs = [f"offsetof(mr_counters, {f})" for f in cnt] + \
+           [f"offsetof(mro_result, {f})" for f in oracle_lib.COUNTER_KEYS]
     src = f"""
 #include <stdio.h>
 #include <stddef.h>
-#include "{HEADER}"
+#include "{os.path.join(ROOT, "oracle", "mr_oracle.h")}"
 int main(void) {{
-  printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(mr_cfg), sizeof(mr_counters), sizeof(mr_run_stats),
-         sizeof(mr_event), offsetof(mr_cfg, device), offsetof(mr_counters, fail_hist));
+  size_t v[] = {{sizeof(mr_cfg), sizeof(mr_counters), sizeof(mr_run_stats), sizeof(mr_event),
+                offsetof(mr_cfg, device), offsetof(mr_counters, fail_hist), sizeof(mro_result),
+                {", ".join(offs)}}};
+  for (size_t i = 0; i < sizeof v / sizeof *v; i++) printf("%zu ", v[i]);
   return 0;
 }}"""
     with tempfile.TemporaryDirectory() as d:
@@ -57,7 +82,21 @@ int main(void) {{
                                            check=True).stdout.split()))
     assert got == [C.sizeof(_abi.MrCfg), C.sizeof(_abi.MrCounters), C.sizeof(_abi.MrRunStats),
                    _abi.EVENT_DTYPE.itemsize, _abi.MrCfg.device.offset,
-                   _abi.MrCounters.fail_hist.offset]
+                   _abi.MrCounters.fail_hist.offset, C.sizeof(oracle_lib.MroResult)] + \
+        [getattr(_abi.MrCounters, f).offset for f in cnt] + \
+        [getattr(oracle_lib.MroResult, f).offset for f in oracle_lib.COUNTER_KEYS]
+
+
+def test_counter_table_names_the_key_lists():
+    """The counter table's MAX rows are its tail, and the key lists derived from it (dist.py's
+    reductions, the parity tests' comparison) hold exactly the keys they held when typed out."""
+    red = [r.reduce for r in _abi.COUNTER_ROWS]
+    assert red == sorted(red, reverse=True) and red.count("MAX") == 3  # "SUM" rows, then "MAX"
+    assert set(mdist.SUM_KEYS) == set(PINNED_SUM_KEYS) and len(mdist.SUM_KEYS) == len(PINNED_SUM_KEYS)
+    assert mdist.MAX_KEYS == PINNED_MAX_KEYS
+    assert sorted(oracle_lib.COUNTER_KEYS) == sorted(PINNED_PARITY_KEYS)
+    assert {r.field for r in _abi.COUNTER_ROWS if r.who == "HIP"} == \
+        {"entries_materialized", "coop_entries"}
 
 
 def test_scenario_names_roundtrip(L):
@@ -122,6 +161,10 @@ def test_table_parser_rejects_a_row_it_cannot_read(tmp_path, monkeypatch):
     monkeypatch.setattr(_abi, "HEADER", str(bad))
     with pytest.raises(ValueError, match="FAIL_X"):
         _abi._table("MR_FAIL_TABLE")
+    bad.write_text('#define MR_COUNTER_TABLE(X) \\\n  X(EV_MSG, ev_msg, SUM, BOTH) \\\n'
+                   '  X(EV_TIMER, ev_timer, MIN, BOTH)\n')
+    with pytest.raises(ValueError, match="EV_TIMER"):
+        _abi._table("MR_COUNTER_TABLE", _abi._COUNTER_ROW)
 
 
 def test_scenario_table_matches_library(L):
@@ -135,6 +178,42 @@ def test_scenario_table_matches_library(L):
         assert (cfg.scenario, cfg.n_nodes, cfg.msg_slots) == (r.id, r.servers, r.slots), r.name
     assert L.mr_scenario_name(len(_abi.SCENARIOS)).decode() == ""
     assert L.mr_cfg_init(C.byref(_abi.MrCfg()), len(_abi.SCENARIOS)) != 0
+
+
+def test_oracle_reads_the_scenario_and_verdict_tables(oracle):
+    """The oracle twin of test_scenario_table_matches_library / test_fail_table_matches_library:
+    its names and messages are the header's rows."""
+    msg = oracle.L.mro_fail_message
+    msg.argtypes, msg.restype = [C.c_uint32], C.c_char_p
+    for r in _abi.SCENARIO_ROWS:
+        assert oracle.L.mro_scenario_from_name(r.name.encode()) == r.id
+    assert oracle.L.mro_scenario_from_name(b"no_such_test") == 0
+    rows = _abi._table("MR_FAIL_TABLE")
+    assert len(rows) >= 57
+    for code, _, text, *_ in rows:
+        assert msg(int(code, 0)).decode() == text
+    for c in (set(range(64)) | {0xFFFE, 0x10000}) - {int(r[0], 0) for r in rows}:
+        assert msg(c) == b"unknown", c
+
+
+@pytest.mark.parametrize("field,value,message", [
+    ("n_nodes", 9, "n_nodes must be 3..8"), ("log_cap", 1000, "log_cap: power of 2 >= 16"),
+    ("apply_cap", 8, "apply_cap too small"), ("ae_max", 33, "ae_max must be 1..32"),
+    ("msg_slots", 65, "msg_slots must be 1..64 (1..256 for snapshot_recover_many_clients_3b)")])
+def test_capacity_checks_are_shared_with_the_oracle(L, oracle, field, value, message):
+    """mr_cfg_check_caps: the library refuses the config with the message it always gave, and
+    the oracle refuses it too (a raw call: oracle_lib.run_cluster asserts)."""
+    cfg = sim.make_cfg("initial_election_2a")
+    setattr(cfg, field, value)
+    with pytest.raises(sim.SimError, match=re.escape(message)):
+        sim.Batch(cfg=cfg)
+    assert oracle.L.mro_run_cluster(C.byref(cfg), 0, None, None, 0, None) != 0
+
+
+def test_oracle_accepts_wide_slots_where_the_library_does(oracle):
+    """More than 64 message slots are for snapshot_recover_many_clients_3b alone, on both sides."""
+    cfg = oracle.cfg("snapshot_recover_many_clients_3b", msg_slots=65, flags=_abi.MR_F_NULL_RAFT)
+    assert oracle.L.mro_run_cluster(C.byref(cfg), 0, None, None, 0, None) == 0
 
 
 PREDICATES_SRC = """

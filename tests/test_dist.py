@@ -19,7 +19,7 @@ from madraft_amd import dist as mdist
 from madraft_amd._abi import FAIL_NAMES
 
 KEYS_SUM = ["events", "msgs_sent", "drop_loss", "applies", "elections"]
-KEYS_MAX = ["max_inflight", "max_log", "max_index"]
+KEYS_MAX = mdist.MAX_KEYS
 
 
 def _free_port():

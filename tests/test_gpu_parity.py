@@ -13,15 +13,11 @@ import numpy as np
 import pytest
 
 from madraft_amd import _abi
+from tests.oracle_lib import COUNTER_KEYS
 
 pytestmark = pytest.mark.gpu
 
 SUPPORTED = [n for n in _abi.SCENARIOS if n and n not in _abi.GPU_UNSUPPORTED]
-COUNTER_KEYS = ["events", "ev_msg", "ev_timer", "ev_tester", "msgs_sent", "drop_clog",
-                "drop_loss", "drop_overflow", "drop_deliver", "drop_stale", "elections",
-                "leaders_elected", "applies", "snapshots", "installs", "entries_shipped",
-                "max_inflight", "max_log", "max_index", "kv_ops", "kv_checked", "log_writes",
-                "kv_lin_checked"]
 
 
 def first_diff(a, b):
@@ -455,3 +451,54 @@ def test_pool_workgroup_streaming_counters(hip, monkeypatch):
         assert np.array_equal(a, c)
     for k in COUNTER_KEYS:
         assert cp[k] == cs[k], k
+
+
+REDUCE_CHILD = r"""
+import json, sys
+from madraft_amd import sim
+test, null_raft = json.loads(sys.argv[1])
+with sim.Batch(test, 256, null_raft=null_raft, cluster_base=1000) as b:
+    b.run()
+    code, t, _ = b.verdicts()
+    print(json.dumps([b.kernel, code.tolist(), t.tolist(), b.counters()]))
+"""
+
+
+@pytest.mark.parametrize("kernel", ["pool_kernel", "step_kernel"])
+@pytest.mark.parametrize("test,null_raft", [("initial_election_2a", True), ("fail_agree_2b", False)])
+def test_reduce_vector_scalars(hip, oracle, test, null_raft, kernel):
+    """The reduce kernel's output slots no other parity test reads (mr_dev.h RED_VTIME, RED_DONE /
+    RED_PASSED, RED_FIRST_FAIL, RED_FAIL_HIST), against the batch's own verdicts and the oracle:
+    every cluster failing (the null node's ONE_LEADER_NONE, README.md:44-48) and a passing body,
+    through the pool kernel and through the step kernel (MR_POOL=0 is read when the batch is
+    created: a fresh child process), at a cluster base other than 0."""
+    import json
+    import os
+    import subprocess
+    import sys
+    env = dict(os.environ, MR_POOL="0" if kernel == "step_kernel" else "1")
+    p = subprocess.run([sys.executable, "-c", REDUCE_CHILD, json.dumps([test, null_raft])],
+                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), env=env,
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-3000:]
+    kern, code, t, cnt = json.loads(p.stdout.strip().splitlines()[-1])
+    assert kern == kernel
+    code, t = np.array(code), np.array(t)
+    cfg = hip.make_cfg(test, 256, null_raft=null_raft, cluster_base=1000)
+    ocode, ot, _, osum = oracle.run_batch(cfg, 0, 256)
+    assert np.array_equal(code, ocode) and np.array_equal(t, ot)
+    if null_raft:
+        assert (code == 1).all()  # ONE_LEADER_NONE
+    assert cnt["clusters"] == cnt["done"] == 256
+    assert cnt["virt_time_us"] == int(t.astype(np.int64).sum())
+    assert cnt["passed"] == int((code == 0).sum()) and cnt["failed"] == cnt["done"] - cnt["passed"]
+    assert cnt["fail_hist"] == {_abi.FAIL_NAMES[int(c)]: int(n)
+                                for c, n in zip(*np.unique(code, return_counts=True))}
+    bad = np.nonzero(code != 0)[0]
+    if bad.size:
+        assert cnt["first_fail_cluster"] == 1000 + int(bad[0])
+        assert cnt["first_fail_code"] == int(code[bad[0]])
+    else:
+        assert cnt["first_fail_cluster"] == (1 << 64) - 1 and cnt["first_fail_code"] == 0
+    for k in COUNTER_KEYS:
+        assert cnt[k] == osum[k], (test, k, cnt[k], osum[k])
