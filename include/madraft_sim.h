@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MR_ABI_VERSION 4u
+#define MR_ABI_VERSION 5u
 #define MR_MAX_NODES 8u
 #define MR_MAX_MSG_SLOTS 256u
 #define MR_MAX_AE 32u
@@ -483,7 +483,7 @@ int mr_trace_digests(mr_batch* b, uint32_t k, uint64_t* out, size_t cap, size_t*
  * the real strings (tests/test_kv_trace.py). */
 int mr_trace_applies(mr_batch* b, uint32_t k, uint64_t* out, size_t cap, size_t* n);
 /* ABI 4: the kernel the batch's launches run: "pool_kernel", "step_kernel" or
- * "step_kernel_tape" (keyed decisions set or recorded) */
+ * "step_kernel_tape" (keyed decisions or variants set, or decisions recorded) */
 const char* mr_batch_kernel(const mr_batch* b);
 void mr_batch_destroy(mr_batch* b);
 
@@ -517,6 +517,20 @@ int mr_batch_set_decisions(mr_batch* b, const mr_decision* d, size_t n);
 /* Cluster k: with MR_F_RECORD its decisions so far in draw order (*n = decisions drawn, up to
  * cap copied); with decisions set, *n = its draws that found no record (misses). */
 int mr_batch_get_decisions(mr_batch* b, uint32_t k, mr_decision* out, size_t cap, size_t* n);
+/* ABI 5: every cluster of the batch is a variant of cluster 0's seed (seed_base + cluster_base):
+ * base decisions (d.cluster ignored), edits (key must be in base; w0, w1 replace the record's),
+ * masks[c * W + j / 32] bit j % 32 = cluster c applies edit j, W = (n_edits + 31) / 32
+ * (masks == NULL: no cluster applies any). n == 0 drops the variants (Philox again); tables of
+ * another kind (mr_batch_set_decisions) are not a variant's to drop and stay as they are.
+ * A draw whose key is not in base takes that seed's Philox draw, whatever the cluster, and counts
+ * as a miss (mr_batch_get_decisions(b, k, NULL, 0, &n)). Errors, which leave the batch's tables
+ * as they were: a duplicate key in base or in edits, an edit key absent from base, a bad stream,
+ * a MR_F_RECORD batch. The tables survive mr_batch_reset (docs/SEMANTICS.md §12.1). */
+int mr_batch_set_variants(mr_batch* b, const mr_decision* base, size_t n,
+                          const mr_decision* edits, size_t n_edits, const uint32_t* masks);
+/* New masks for the same base and edits: the only upload of a shrinking round. An error
+ * without variants set. */
+int mr_batch_set_variant_masks(mr_batch* b, const uint32_t* masks);
 /* One cluster of cfg (cluster_base selects the seed for misses) driven by the n decisions:
  * its per-event trace (per-node term / role / commit / applied / last / snapshot after every
  * event), its verdict and verdict time, and (misses != NULL) its draws not in `d`. */

@@ -1,12 +1,13 @@
 """CLI: `python -m madraft_amd <test> [--clusters N] [--seed S]` — the batched
 analogue of `MADSIM_TEST_SEED=S MADSIM_TEST_NUM=N cargo test <test>`;
 `--replay log.jsonl` plays one cluster driven by an event-level decision log
-(madraft_amd/trace.py) and prints its verdict."""
+(madraft_amd/trace.py) and prints its verdict; `--seed S --shrink` shrinks a failing seed to a
+1-minimal set of dropped (or delayed) messages (madraft_amd/shrink.py)."""
 import argparse
 import json
 import time
 
-from . import _abi, sim, trace
+from . import _abi, shrink, sim, trace
 
 
 # test bodies that switch the net back to reliable part-way (tests.rs:680 unreliable_agree_2c
@@ -44,6 +45,12 @@ def main():
     ap.add_argument("--bug", choices=["vote_twice", "vote_stale", "no_prev_check"],
                     help="run a known-buggy Raft variant")
     ap.add_argument("--replay", metavar="LOG", help="JSON-lines decision log (trace.py) to replay")
+    ap.add_argument("--shrink", action="store_true",
+                    help="shrink the failing --seed to the faults that cause it (shrink.py)")
+    ap.add_argument("--shrink-kinds", default="drop", metavar="KINDS",
+                    help="fault kinds to shrink, comma-separated: drop, delay (default drop)")
+    ap.add_argument("--shrink-tape", metavar="LOG",
+                    help="with --shrink: write the minimal run's whole tape as a --replay log")
     a = ap.parse_args()
     flags = 0
     if a.bug:
@@ -57,6 +64,22 @@ def main():
         print(json.dumps({"code": code, "verdict": _abi.FAIL_NAMES.get(code, str(code)),
                           "time_us": tm, "events": int(tr.size), "misses": misses}))
         raise SystemExit(0 if code == _abi.MR_PASS else 1)
+    if a.shrink:
+        seed = _abi.README_SEED if a.seed is None else a.seed
+        r = shrink.shrink_seed(a.test, seed, kinds=tuple(a.shrink_kinds.split(",")), nodes=a.nodes,
+                               iters=a.iters, unreliable=a.unreliable, null_raft=a.null,
+                               safety=a.safety, flags=flags)
+        # the kept decisions as --replay lines: decoded where the test's sends have one network
+        # mode, else as raw draw words
+        mode = net_mode(a.test, a.unreliable)
+        kept = trace.events_from_decisions(r.kept, unreliable=bool(mode), raw=mode is None)
+        if a.shrink_tape:
+            trace.dump_jsonl(a.shrink_tape, r.tape, raw=True)
+        print(json.dumps({"code": r.code, "verdict": _abi.FAIL_NAMES.get(r.code, str(r.code)),
+                          "seed": seed, "kind": r.kind, "faults_before": r.faults,
+                          "faults_after": int(r.kept.size), "rounds": r.rounds,
+                          "candidates": r.candidates, "events": int(r.trace.size), "kept": kept}))
+        raise SystemExit(0)
     t0 = time.time()
     code, _, _, cnt = sim.run_test(a.test, a.seed, a.clusters, nodes=a.nodes, iters=a.iters,
                                    unreliable=a.unreliable, null_raft=a.null, safety=a.safety,

@@ -10,7 +10,7 @@ import re
 
 import numpy as np
 
-MR_ABI_VERSION = 4
+MR_ABI_VERSION = 5
 MR_MAX_NODES = 8
 MR_RUNNING = 0xFFFF
 MR_PASS = 0
@@ -178,4 +178,5 @@ EXPORTS = [
     "mr_batch_counters", "mr_trace_get", "mr_batch_destroy", "mr_batch_set_decisions",
     "mr_batch_get_decisions", "mr_decision_word", "mr_replay", "mr_batch_submit", "mr_batch_finish",
     "mr_trace_digests", "mr_trace_applies", "mr_batch_kernel",  # ABI 4
+    "mr_batch_set_variants", "mr_batch_set_variant_masks",  # ABI 5
 ]

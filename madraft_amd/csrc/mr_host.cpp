@@ -129,6 +129,9 @@ struct mr_batch {
   uint32_t budget = 16384;  // events per cluster per launch (MR_STEP_BUDGET)
   uint4* tape = nullptr;     // keyed decisions (own allocation: set_decisions / MR_F_RECORD)
   uint32_t* doff = nullptr;  // replay: CSR row offsets of `tape` (set_decisions)
+  uint32_t* vedit = nullptr;  // variants (set_variants): `tape` = the base tape, its edit indices,
+  uint2* vwords = nullptr;    // the edits' words,
+  uint32_t* vmask = nullptr;  // and the clusters' mask rows (set_variant_masks rewrites them)
   bool submitted = false;    // mr_batch_submit enqueued a step not yet finished
   uint32_t kern = 0;         // kernel family of the launches since the reset: 1 pool, 2 step / tape
   std::chrono::steady_clock::time_point t_submit;
@@ -653,13 +656,19 @@ uint32_t mr_decision_word(uint32_t v, uint32_t lo, uint32_t hi) {
   return (uint32_t)((num + span - 1) / span);
 }
 
-// the batch's decision tables (replay rows + offsets, or the record tape) freed; Philox draws
+// the batch's decision tables (replay rows + offsets, the record tape, or a variant batch's
+// base tape, edits and masks) freed; Philox draws
 static void drop_decisions(mr_batch* b) {
   if (b->tape) (void)hipFree(b->tape);
   if (b->doff) (void)hipFree(b->doff);
+  if (b->vedit) (void)hipFree(b->vedit);
+  if (b->vwords) (void)hipFree(b->vwords);
+  if (b->vmask) (void)hipFree(b->vmask);
   b->tape = nullptr;
   b->doff = nullptr;
+  b->vedit = nullptr; b->vwords = nullptr; b->vmask = nullptr;
   b->D.dtab = nullptr; b->D.doff = nullptr; b->D.dcap = 0; b->D.tape_mode = 0;
+  b->D.vedit = nullptr; b->D.vwords = nullptr; b->D.vmask = nullptr; b->D.vn = 0; b->D.vW = 0;
 }
 
 // Keyed decisions as CSR rows: every decision once (16 B each) plus C + 1 offsets, so the
@@ -719,6 +728,97 @@ int mr_batch_set_decisions(mr_batch* b, const mr_decision* d, size_t n) {
   HIPCHK(hipStreamSynchronize(b->stream));
   if (!n) { drop_decisions(b); return 0; }
   return no_throw("decision table", [&] { return set_decisions_impl(b, d, n); });  // host staging
+}
+
+// A variant batch (madraft_sim.h mr_batch_set_variants): the base tape sorted once, each base
+// record's edit index beside it, the edits' words, and one mask row per cluster. Validated and
+// staged whole before the previous tables are dropped, like set_decisions_impl.
+static int set_variants_impl(mr_batch* b, const mr_decision* base, size_t n, const mr_decision* edits,
+                             size_t n_edits, const uint32_t* masks) {
+  const size_t C = b->D.C;
+  if (n >= (1ull << 32) || n_edits >= (1ull << 32))
+    return set_err("too many decisions for one batch (2^32 - 1 at most)");
+  auto key_of = [](const mr_decision& r) { return make_uint2(((uint32_t)r.stream << 16) | r.entity, r.seq); };
+  auto bad_stream = [](const mr_decision& r) { return r.stream < MR_DS_TESTER || r.stream > MR_DS_NET; };
+  std::vector<uint4> tab(n);
+  for (size_t i = 0; i < n; i++) {
+    if (bad_stream(base[i])) return set_err("bad decision stream");
+    const uint2 k = key_of(base[i]);
+    tab[i] = make_uint4(k.x, k.y, base[i].w0, base[i].w1);
+  }
+  auto lt = [](const uint4& a, const uint4& c) { return a.x < c.x || (a.x == c.x && a.y < c.y); };
+  std::sort(tab.begin(), tab.end(), lt);
+  for (size_t k = 1; k < n; k++)
+    if (tab[k].x == tab[k - 1].x && tab[k].y == tab[k - 1].y)
+      return set_err("duplicate decision key in the base tape");
+  std::vector<uint32_t> ved(n, ~0u);
+  std::vector<uint2> vw(n_edits);
+  for (size_t j = 0; j < n_edits; j++) {
+    if (bad_stream(edits[j])) return set_err("bad decision stream (edit " + std::to_string(j) + ")");
+    const uint2 k = key_of(edits[j]);
+    auto it = std::lower_bound(tab.begin(), tab.end(), make_uint4(k.x, k.y, 0, 0), lt);
+    if (it == tab.end() || it->x != k.x || it->y != k.y)
+      return set_err("edit " + std::to_string(j) + ": its key is not in the base tape");
+    uint32_t& e = ved[it - tab.begin()];
+    if (e != ~0u) return set_err("duplicate edit key (edits " + std::to_string(e) + " and " + std::to_string(j) + ")");
+    e = (uint32_t)j;
+    vw[j] = make_uint2(edits[j].w0, edits[j].w1);
+  }
+  const size_t W = (n_edits + 31) / 32, mw = C * W;
+  uint4* dtab = nullptr;
+  uint32_t *dved = nullptr, *dmask = nullptr;
+  uint2* dvw = nullptr;
+  hipError_t e = hipMalloc(&dtab, n * sizeof(uint4));
+  if (e == hipSuccess) e = hipMalloc(&dved, n * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&dvw, (n_edits ? n_edits : 1) * sizeof(uint2));
+  if (e == hipSuccess) e = hipMalloc(&dmask, (mw ? mw : 1) * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemcpy(dtab, tab.data(), n * sizeof(uint4), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dved, ved.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess && n_edits)
+    e = hipMemcpy(dvw, vw.data(), n_edits * sizeof(uint2), hipMemcpyHostToDevice);
+  if (e == hipSuccess && mw)
+    e = masks ? hipMemcpy(dmask, masks, mw * sizeof(uint32_t), hipMemcpyHostToDevice)
+              : hipMemset(dmask, 0, mw * sizeof(uint32_t));
+  if (e != hipSuccess) {
+    if (dtab) (void)hipFree(dtab);
+    if (dved) (void)hipFree(dved);
+    if (dvw) (void)hipFree(dvw);
+    if (dmask) (void)hipFree(dmask);
+    return set_err(std::string("variant tables: ") + hipGetErrorString(e));
+  }
+  drop_decisions(b);
+  b->tape = dtab; b->vedit = dved; b->vwords = dvw; b->vmask = dmask;
+  b->D.dtab = dtab; b->D.vedit = dved; b->D.vwords = dvw; b->D.vmask = dmask;
+  b->D.vn = (uint32_t)n; b->D.vW = (uint32_t)W;
+  b->D.tape_mode = 3;
+  return 0;
+}
+
+int mr_batch_set_variants(mr_batch* b, const mr_decision* base, size_t n, const mr_decision* edits,
+                          size_t n_edits, const uint32_t* masks) {
+  if (!b) return set_err("null batch");
+  if (b->cfg.flags & MR_F_RECORD) return set_err("variants on a MR_F_RECORD batch");
+  if (n && !base) return set_err("null decisions");
+  if (n && n_edits && !edits) return set_err("null edits");
+  HIPCHK(hipSetDevice(b->cfg.device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (!n) {
+    if (b->D.tape_mode == 3u) drop_decisions(b);  // (another kind of table is not a variant's to drop)
+    return 0;
+  }
+  return no_throw("variant tables", [&] { return set_variants_impl(b, base, n, edits, n_edits, masks); });
+}
+
+int mr_batch_set_variant_masks(mr_batch* b, const uint32_t* masks) {
+  if (!b) return set_err("null batch");
+  if (b->D.tape_mode != 3u) return set_err("mr_batch_set_variant_masks without variants");
+  HIPCHK(hipSetDevice(b->cfg.device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  const size_t mw = (size_t)b->D.C * b->D.vW;
+  if (!mw) return 0;
+  if (masks) HIPCHK(hipMemcpy(b->vmask, masks, mw * sizeof(uint32_t), hipMemcpyHostToDevice));
+  else HIPCHK(hipMemset(b->vmask, 0, mw * sizeof(uint32_t)));
+  return 0;
 }
 
 static int mr_batch_get_decisions_impl(mr_batch* b, uint32_t k, mr_decision* out, size_t cap, size_t* n) {
@@ -793,6 +893,9 @@ void mr_batch_destroy(mr_batch* b) {
   if (b->base) (void)hipFree(b->base);
   if (b->tape) (void)hipFree(b->tape);
   if (b->doff) (void)hipFree(b->doff);
+  if (b->vedit) (void)hipFree(b->vedit);
+  if (b->vwords) (void)hipFree(b->vwords);
+  if (b->vmask) (void)hipFree(b->vmask);
   // the streaming held-cluster lists belong to the batch, not to its decision tables
   for (uint32_t h = 0; h < 2; h++)
     if (b->held[h]) { (void)hipFree(b->held[h]); b->held[h] = nullptr; }

@@ -1,0 +1,211 @@
+"""Shrink a failing seed to the faults that cause it (docs/SEMANTICS.md §12.1).
+
+A recorded run is a set of keyed decisions. Some of them are faults: a dropped message, a
+long latency. An edit takes one fault away (the message is delivered, the latency is 1 ms);
+a candidate is the set of faults it keeps, every other fault edited away. `shrink` is delta
+debugging (ddmin, Zeller & Hildebrandt 2002) over such sets with every round's candidates
+evaluated at once; `shrink_seed` evaluates a round as one variant batch on the GPU
+(`Batch.set_variants`): one shared base tape, one mask row per candidate.
+"""
+import collections
+
+import numpy as np
+
+from . import _abi
+from ._abi import DECISION_DTYPE, LOSS_Q32, MR_DS_NET
+
+KINDS = ("drop", "delay")
+
+Shrunk = collections.namedtuple("Shrunk", "kept rounds candidates")
+ShrunkSeed = collections.namedtuple(
+    "ShrunkSeed", "kept kind code trace tape faults rounds candidates")
+
+
+def max_candidates(n_faults):
+    """The most candidates one `evaluate` call of shrink(.., n_faults, ..) submits."""
+    return max(2, 2 * n_faults)
+
+
+def shrink(evaluate, n_faults, target):
+    """A 1-minimal subset of the faults 0..n_faults-1 that still fails.
+
+    `evaluate(keep)` takes a bool array [candidates, n_faults] (row = the faults a candidate
+    keeps) and returns one verdict code per row; a candidate fails when its code == target.
+    The result is a function of those verdicts alone, by this policy:
+
+    1. The first call submits the empty set and the full set, in that order. If the empty set
+       fails the result is empty; if the full set does not fail, ValueError.
+    2. Then ddmin on the current set (at first all faults, ascending) at granularity g (at first
+       2): the set is cut into g contiguous chunks whose sizes differ by at most one, the larger
+       first. One call submits the g chunks and then, where g > 2, the g complements (the set
+       without chunk 0, without chunk 1, ...). The first failing candidate in that order
+       becomes the current set: after a chunk g = 2, after a complement g = max(g - 1, 2).
+       If none fails, g doubles (at most the set's size); if g was the set's size already, the
+       round was the single-removal check — no chunk of one fault and no set with one fault
+       removed fails — and the set is 1-minimal: done. A set of one fault is 1-minimal by
+       step 1.
+
+    Returns Shrunk(kept: ascending indices, rounds: evaluate calls, candidates: rows submitted).
+    """
+    n = int(n_faults)
+
+    def rows(sets):
+        keep = np.zeros((len(sets), n), bool)
+        for r, s in enumerate(sets):
+            keep[r, s] = True
+        return keep
+
+    def failing(sets):
+        codes = np.asarray(evaluate(rows(sets)))
+        assert codes.shape == (len(sets),), codes.shape
+        return codes == target
+
+    cur = np.arange(n)
+    rounds, cands = 1, 2
+    empty_fails, full_fails = failing([cur[:0], cur])
+    if empty_fails:
+        return Shrunk(cur[:0], rounds, cands)
+    if not full_fails:
+        raise ValueError("the run with every fault kept does not fail with the target verdict")
+    g = 2
+    while cur.size >= 2:
+        chunks = np.array_split(cur, g)
+        sets = list(chunks)
+        if g > 2:
+            sets += [np.concatenate(chunks[:i] + chunks[i + 1:]) for i in range(g)]
+        rounds += 1
+        cands += len(sets)
+        hit = np.nonzero(failing(sets))[0]
+        if hit.size:
+            cur = sets[hit[0]]
+            g = 2 if hit[0] < len(chunks) else max(g - 1, 2)
+        elif g < cur.size:
+            g = min(2 * g, cur.size)
+        else:
+            break
+    return Shrunk(cur, rounds, cands)
+
+
+def find_edits(base, kind):
+    """(indices into `base`, edits) of one kind: `drop` — a NET record with w0 < LOSS_Q32,
+    edited to w0 = 0xFFFFFFFF (delivered, latency kept); `delay` — a NET record that is no
+    drop with w1 >= 2^31 (the upper half of the latency range), edited to w1 = 0 (1 ms)."""
+    base = np.asarray(base, DECISION_DTYPE)
+    net = base["stream"] == MR_DS_NET
+    drop = net & (base["w0"] < LOSS_Q32)
+    if kind == "drop":
+        idx = np.nonzero(drop)[0]
+        edits = base[idx].copy()
+        edits["w0"] = 0xFFFFFFFF
+    elif kind == "delay":
+        idx = np.nonzero(net & ~drop & (base["w1"] >= 1 << 31))[0]
+        edits = base[idx].copy()
+        edits["w1"] = 0
+    else:
+        raise ValueError(f"unknown edit kind {kind!r} (one of {KINDS})")
+    return idx, edits
+
+
+def apply_edits(base, idx, edits, applied):
+    """`base` with edits[j] in place of base[idx[j]] wherever applied[j]: the tape one variant
+    replays, for mr_replay or the oracle."""
+    out = np.array(base, DECISION_DTYPE)
+    applied = np.asarray(applied, bool)
+    out[idx[applied]] = edits[applied]
+    return out
+
+
+Passes = collections.namedtuple("Passes", "kind kept applied faults rounds candidates idx edits")
+
+
+def edit_list(base, kinds):
+    """(idx, edits, kind per edit) of every kind in `kinds`, drops before delays: the edits of
+    one variant batch. The kinds' records are disjoint, so no key is edited twice."""
+    parts = [(k, *find_edits(base, k)) for k in KINDS if k in kinds]
+    if not parts or set(kinds) - set(KINDS):
+        raise ValueError(f"edit kinds {kinds!r}: some of {KINDS}")
+    return (np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts]),
+            np.concatenate([np.full(p[1].size, p[0]) for p in parts]))
+
+
+def shrink_passes(evaluate_masks, base, kinds, target):
+    """The passes of a seed's shrinking over `evaluate_masks(applied[candidates, n_edits]) ->
+    codes` (column j = edit j of edit_list(base, kinds)), whatever runs the candidates — a
+    variant batch, the oracle. Drops first, with no delay edited; if the empty drop set still
+    fails (loss is not the cause) and `kinds` names delays, delays with every drop delivered.
+
+    Returns Passes: the kind that was shrunk last, kept (positions in the edit list of the
+    faults that stay), applied (the minimal run's edits), that kind's faults before, evaluate
+    calls and candidates over all passes, and the edit list's idx and edits."""
+    idx, edits, kind_of = edit_list(base, kinds)
+    fixed = np.zeros(idx.size, bool)  # edits applied in every candidate of the pass
+    rounds = cands = 0
+    order = [k for k in KINDS if k in kinds]
+    for kind in order:
+        mine = np.nonzero(kind_of == kind)[0]
+
+        def evaluate(keep):
+            applied = np.tile(fixed, (keep.shape[0], 1))
+            applied[:, mine] = ~keep
+            return evaluate_masks(applied)
+
+        res = shrink(evaluate, mine.size, target)
+        rounds += res.rounds
+        cands += res.candidates
+        fixed[mine] = True  # (a kind that is not the cause stays edited away in the next pass)
+        if res.kept.size or kind == order[-1]:
+            applied = fixed.copy()
+            applied[mine[res.kept]] = False
+            return Passes(kind, mine[res.kept], applied, mine.size, rounds, cands, idx, edits)
+
+
+def n_variants(base, kinds):
+    """Clusters of the variant batch that serves every round of shrink_passes(.., base, kinds)."""
+    return max(max_candidates(find_edits(base, k)[0].size) for k in KINDS if k in kinds)
+
+
+def shrink_seed(test, seed, kinds=("drop",), tape_cap=1 << 16, **cfg_kw):
+    """Shrink the failing run of `test` at `seed` (make_cfg's keywords: iters, flags, ...) to a
+    1-minimal set of faults of `kinds` on the GPU: the seed is recorded (MR_F_RECORD, one
+    cluster), then every ddmin round is one run of one variant batch whose masks are the
+    round's candidates (unused clusters repeat candidate 0).
+
+    Returns ShrunkSeed: kept (the base records of the faults that stay, DECISION_DTYPE), their
+    kind, the verdict code, the minimal run's trace (mr_replay of its tape), that tape, the
+    faults of that kind before, evaluate rounds and candidates run."""
+    from . import sim
+    flags = int(cfg_kw.pop("flags", 0))
+    base_c = int(cfg_kw.pop("cluster_base", 0))
+    seed_base = int(seed) - base_c  # cluster 0's seed (seed_base + cluster_base) is `seed`
+    with sim.Batch(test, 1, seed_base, cluster_base=base_c, flags=flags | _abi.MR_F_RECORD,
+                   tape_cap=tape_cap, **cfg_kw) as b:
+        b.run()
+        target = int(b.verdicts()[0][0])
+        n, base = b.decisions(0, tape_cap)
+    if n > tape_cap:
+        raise sim.SimError(f"tape_cap {tape_cap} too small: the seed draws {n} decisions")
+    if target == _abi.MR_PASS:
+        raise sim.SimError(f"seed {seed} passes {test}: nothing to shrink")
+    base = base.copy()
+    clusters = n_variants(base, kinds)
+    with sim.Batch(test, clusters, seed_base, cluster_base=base_c, flags=flags, **cfg_kw) as b:
+        b.set_variants(base, edit_list(base, kinds)[1])
+
+        def evaluate_masks(applied):
+            m = np.empty((clusters, applied.shape[1]), bool)
+            m[: applied.shape[0]] = applied
+            m[applied.shape[0]:] = applied[0]
+            b.set_variant_masks(m)
+            b.reset(seed_base)
+            st = b.run()
+            assert st["remaining"] == 0, st
+            return b.verdicts()[0][: applied.shape[0]]
+
+        p = shrink_passes(evaluate_masks, base, kinds, target)
+    tape = apply_edits(base, p.idx, p.edits, p.applied)
+    tr, code, _, _ = sim.replay(test, tape, seed=seed_base, cluster_base=base_c, flags=flags,
+                                **cfg_kw)
+    if code != target:
+        raise sim.SimError(f"the minimal tape replays to verdict {code}, not {target}")
+    return ShrunkSeed(base[p.idx[p.kept]], p.kind, target, tr, tape, p.faults, p.rounds,
+                      p.candidates)

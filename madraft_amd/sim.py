@@ -57,6 +57,9 @@ def lib():
     L.mr_batch_set_decisions.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.mr_batch_get_decisions.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
                                          C.POINTER(C.c_size_t)]
+    L.mr_batch_set_variants.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]
+    L.mr_batch_set_variant_masks.argtypes = [C.c_void_p, C.c_void_p]
     L.mr_decision_word.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     L.mr_decision_word.restype = C.c_uint32
     L.mr_replay.argtypes = [C.POINTER(MrCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
@@ -135,6 +138,7 @@ class Batch:
     def __init__(self, test=None, clusters=1, seed=_abi.README_SEED, *, cfg=None, **kw):
         self.cfg = cfg if cfg is not None else make_cfg(test, clusters, seed, **kw)
         self._b = C.c_void_p()
+        self._n_edits = 0  # edits of the variants set (set_variants)
         _check(lib().mr_batch_create(C.byref(self.cfg), C.byref(self._b)))
 
     @property
@@ -194,9 +198,52 @@ class Batch:
         SEMANTICS §12); None = Philox again. Call before run()."""
         if d is None or len(d) == 0:
             _check(lib().mr_batch_set_decisions(self._b, None, 0))
+            self._n_edits = 0  # (any variants are dropped with the tables)
             return
         a = np.ascontiguousarray(d, dtype=DECISION_DTYPE)
         _check(lib().mr_batch_set_decisions(self._b, a.ctypes.data, a.size))
+        self._n_edits = 0
+
+    def _mask_words(self, masks, n_edits):
+        """[clusters, ceil(n_edits / 32)] uint32 mask rows from a bool array [clusters, n_edits]
+        (True = the cluster applies the edit) or from rows already packed; None stays None."""
+        if masks is None:
+            return None
+        m = np.asarray(masks)
+        w = (n_edits + 31) // 32
+        if m.dtype == np.bool_:
+            if m.shape != (self.clusters, n_edits):
+                raise SimError(f"masks: shape {m.shape}, not ({self.clusters}, {n_edits})")
+            bits = np.zeros((self.clusters, w * 32), np.uint8)
+            bits[:, :n_edits] = m
+            m = np.packbits(bits, axis=1, bitorder="little").view("<u4")
+        m = np.ascontiguousarray(m, dtype=np.uint32)
+        if m.shape != (self.clusters, w):
+            raise SimError(f"masks: shape {m.shape}, not ({self.clusters}, {w})")
+        return m
+
+    def set_variants(self, base, edits=None, masks=None):
+        """Make every cluster a variant of cluster 0's seed (mr_batch_set_variants; SEMANTICS
+        §12.1): `base` decisions shared by all, `edits` that replace the words of base records,
+        `masks` [clusters, len(edits)] bool (or packed uint32 rows) saying which cluster applies
+        which edit (None: none). base None or empty = Philox again."""
+        if base is None or len(base) == 0:
+            _check(lib().mr_batch_set_variants(self._b, None, 0, None, 0, None))
+            self._n_edits = 0
+            return
+        a = np.ascontiguousarray(base, dtype=DECISION_DTYPE)
+        e = np.ascontiguousarray(edits if edits is not None else [], dtype=DECISION_DTYPE)
+        m = self._mask_words(masks, e.size)
+        _check(lib().mr_batch_set_variants(self._b, a.ctypes.data, a.size,
+                                           e.ctypes.data if e.size else None, e.size,
+                                           m.ctypes.data if m is not None and m.size else None))
+        self._n_edits = int(e.size)
+
+    def set_variant_masks(self, masks):
+        """New masks for the variants set (mr_batch_set_variant_masks); then reset() and run()."""
+        m = self._mask_words(masks, self._n_edits)
+        _check(lib().mr_batch_set_variant_masks(self._b, m.ctypes.data if m is not None and m.size
+                                                else None))
 
     def decisions(self, k, cap=1 << 20):
         """(n, records): with MR_F_RECORD cluster k's decisions in draw order (n drawn);
@@ -231,7 +278,8 @@ class Batch:
 
     @property
     def kernel(self):
-        """mr_batch_kernel: "pool_kernel", "step_kernel" or "step_kernel_tape"."""
+        """mr_batch_kernel: "pool_kernel", "step_kernel" or "step_kernel_tape" (decisions,
+        variants or recording)."""
         return lib().mr_batch_kernel(self._b).decode()
 
 
