@@ -2014,66 +2014,98 @@ DI void tester(const Dev& Darg, X& x) {
 // ---------------------------------------------------------------- kernels
 constexpr uint32_t CLS_MSG = 0, CLS_TIMER = 1, CLS_TESTER = 2, CLS_NONE = 3;
 
-// a cluster's run state into the lane (registers, LDS message keys) and back: at the start and
-// end of a launch, and when a lane that finished its cluster takes the next one (D.stream)
+// A cluster's run state between launches (mr_dev.h CS_* / C64_*) and the X member that holds it
+// during one, F(member, field): cluster_load, its consume barrier and cluster_store are generated
+// from these lists; the arrays (node timers, free-slot words, counters, message keys) follow.
+#define X_WORDS(F)                                                                             \
+  F(now, CS_NOW) F(events, CS_EVENTS) F(msgs_sent, CS_MSGS) F(inflight, CS_INFLIGHT)           \
+  F(trace_n, CS_TRACEN) F(mslot, CS_MSLOT) F(netmode, CS_NETMODE) F(t_ctr, CS_TCTR)            \
+  F(conn, CS_CONN) F(alive, CS_ALIVE) F(twake, CS_TWAKE) F(lmask, CS_LMASK)
+#define X_THR_WORDS(F) F(cwake, CS_CWAKE) F(ctid, CS_CTID) F(cslot, CS_CSLOT)  // nthr(S) > 0
+#define X_QUADS(F) F(digest, C64_DIGEST) F(mmin, C64_MMIN)
+#define F_LOAD(m, f) x.m = CS(f);
+#define F_LOAD64(m, f) x.m = C64(f);
+#define F_STORE(m, f) CS(f) = x.m;
+#define F_STORE64(m, f) C64(f) = x.m;
+#define F_USE(m, f) use(x.m);
+DI void use(uint32_t v) { asm volatile("" ::"v"(v)); }
+DI void use(uint64_t v) { asm volatile("" ::"v"(v)); }
+constexpr uint32_t c64_free(uint32_t w) { return w ? C64_FREE1 + w - 1 : C64_FREE; }
+// this counter travels with the cluster: all of them in step_kernel; in pool_kernel a lane keeps
+// the sums of the events it runs (mr_pool.inc), and only the two read per cluster travel
+constexpr bool cnt_travels(uint32_t k) { return !MR_POOL || k == CNT_LEADERS || k == CNT_MAX_INDEX; }
+static_assert(!MR_POOL || MW == 1, "the pool's LDS record keeps one word of free slots");
+
+// a cluster's run state into registers and LDS message keys (the rows in LDS: key_live) and
+// back: at the start and end of a launch, and when a lane or pool slot whose cluster finished
+// takes the next one (D.stream)
 template <uint32_t S>
-DI void lane_load(const Dev& D, X& x) {
+DI void cluster_load(const Dev& D, X& x) {
+  if constexpr (MR_POOL == 2) x.ap0 = 0u;  // (a launch never ends inside an applier continuation)
   x.code = CS(CS_CODE);
   if (x.code != RUN) return;
-  x.now = CS(CS_NOW); x.events = CS(CS_EVENTS); x.msgs_sent = CS(CS_MSGS);
-  x.inflight = CS(CS_INFLIGHT); x.trace_n = CS(CS_TRACEN); x.mslot = CS(CS_MSLOT);
-  x.netmode = CS(CS_NETMODE); x.t_ctr = CS(CS_TCTR);
-  x.conn = CS(CS_CONN); x.alive = CS(CS_ALIVE); x.twake = CS(CS_TWAKE); x.lmask = CS(CS_LMASK);
-  if constexpr (nthr(S) > 0) { x.cwake = CS(CS_CWAKE); x.ctid = CS(CS_CTID); x.cslot = CS(CS_CSLOT); }
+  X_WORDS(F_LOAD)
+  if constexpr (nthr(S) > 0) { X_THR_WORDS(F_LOAD) }
 #pragma unroll
   for (uint32_t d = 0; d < NB; d++) x.timer[d] = d < D.n ? TMR(d) : INF_T;
 #pragma unroll
-  for (uint32_t w = 0; w < MW; w++) x.free_mask[w] = C64(w ? C64_FREE1 + w - 1 : C64_FREE);
-  x.digest = C64(C64_DIGEST); x.mmin = C64(C64_MMIN);
+  for (uint32_t w = 0; w < MW; w++) x.free_mask[w] = C64(c64_free(w));
+  X_QUADS(F_LOAD64)
 #pragma unroll
-  for (uint32_t k = 0; k < CNT__N; k++) x.cnt[k] = CS(CS_CNT + k);
-  for (uint32_t s = 0; s < D.M; s++) LK(s) = (lkey_t)MKEY(s);
+  for (uint32_t k = 0; k < CNT__N; k++)
+    if (cnt_travels(k)) x.cnt[k] = CS(CS_CNT + k);
+  for (uint32_t s = 0; s < key_live(D); s++) LK(s) = (lkey_t)MKEY(s);  // (the rest stay in HBM)
+  if constexpr (MR_POOL == 2) {  // the AppendEntries requests in flight (a resumed cluster)
+    x.aem = 0ull;
+    for (uint64_t occ = ~x.free_mask[0] & (D.M >= 64 ? ~0ull : (1ull << D.M) - 1ull); occ; occ &= occ - 1ull) {
+      const uint32_t s = (uint32_t)__builtin_ctzll(occ);
+      if (hdr_type(MS32(MF_HDR, s)) == M_AE_REQ) x.aem |= 1ull << s;
+    }
+  }
   // every load above completes here (each loaded register is read by an empty asm): a lane that
-  // takes a new cluster inside the step loop (streaming) then leaves no load pending into the
+  // takes a new cluster inside the kernel's loop (streaming) then leaves no load pending into the
   // loop, where the compiler would otherwise place a conservative vmcnt(0) — one that also
   // waits for every store in flight — at the first later use of these registers on EVERY
   // iteration's path
-  asm volatile("" ::"v"(x.now), "v"(x.events), "v"(x.msgs_sent), "v"(x.inflight), "v"(x.trace_n),
-               "v"(x.mslot), "v"(x.netmode), "v"(x.t_ctr), "v"(x.conn), "v"(x.alive), "v"(x.twake),
-               "v"(x.lmask), "v"(x.digest), "v"(x.mmin));
-  if constexpr (nthr(S) > 0) asm volatile("" ::"v"(x.cwake), "v"(x.ctid), "v"(x.cslot));
+  X_WORDS(F_USE)
+  if constexpr (nthr(S) > 0) { X_THR_WORDS(F_USE) }
 #pragma unroll
-  for (uint32_t d = 0; d < NB; d++) asm volatile("" ::"v"(x.timer[d]));
+  for (uint32_t d = 0; d < NB; d++) use(x.timer[d]);
 #pragma unroll
-  for (uint32_t w = 0; w < MW; w++) asm volatile("" ::"v"(x.free_mask[w]));
+  for (uint32_t w = 0; w < MW; w++) use(x.free_mask[w]);
+  X_QUADS(F_USE)
 #pragma unroll
-  for (uint32_t k = 0; k < CNT__N; k++) asm volatile("" ::"v"(x.cnt[k]));
+  for (uint32_t k = 0; k < CNT__N; k++)
+    if (cnt_travels(k)) use(x.cnt[k]);
 }
 template <uint32_t S>
-DI void lane_store(const Dev& D, X& x) {
+DI void cluster_store(const Dev& D, X& x) {
   CS(CS_CODE) = x.code;
   if (x.code != RUN) CS(CS_VTIME) = x.now;
-  CS(CS_NOW) = x.now; CS(CS_EVENTS) = x.events; CS(CS_MSGS) = x.msgs_sent;
-  CS(CS_INFLIGHT) = x.inflight; CS(CS_TRACEN) = x.trace_n; CS(CS_MSLOT) = x.mslot;
-  CS(CS_NETMODE) = x.netmode; CS(CS_TCTR) = x.t_ctr;
-  CS(CS_CONN) = x.conn; CS(CS_ALIVE) = x.alive; CS(CS_TWAKE) = x.twake; CS(CS_LMASK) = x.lmask;
-  if constexpr (nthr(S) > 0) { CS(CS_CWAKE) = x.cwake; CS(CS_CTID) = x.ctid; CS(CS_CSLOT) = x.cslot; }
+  X_WORDS(F_STORE)
+  if constexpr (nthr(S) > 0) { X_THR_WORDS(F_STORE) }
 #pragma unroll
   for (uint32_t d = 0; d < NB; d++)
     if (d < D.n) TMR(d) = x.timer[d];
 #pragma unroll
-  for (uint32_t w = 0; w < MW; w++) C64(w ? C64_FREE1 + w - 1 : C64_FREE) = x.free_mask[w];
-  C64(C64_DIGEST) = x.digest; C64(C64_MMIN) = x.mmin;
+  for (uint32_t w = 0; w < MW; w++) C64(c64_free(w)) = x.free_mask[w];
+  X_QUADS(F_STORE64)
 #pragma unroll
-  for (uint32_t k = 0; k < CNT__N; k++) CS(CS_CNT + k) = x.cnt[k];
+  for (uint32_t k = 0; k < CNT__N; k++)
+    if (cnt_travels(k)) CS(CS_CNT + k) = x.cnt[k];
   if (x.code != RUN) return;  // a finished cluster's messages are never read again
-  for (uint32_t s = 0; s < D.M; s++) MKEY(s) = LK(s) == LKEY_FREE ? ~0ull : (uint64_t)LK(s);
+  for (uint32_t s = 0; s < key_live(D); s++) MKEY(s) = LK(s) == LKEY_FREE ? ~0ull : (uint64_t)LK(s);
 }
+#undef F_LOAD
+#undef F_LOAD64
+#undef F_STORE
+#undef F_STORE64
+#undef F_USE
 // lanes that want a cluster (`want`) take the next unclaimed ones, one atomic per wave per
 // round; a taken cluster that already has its verdict (a later launch of a long run) is
 // skipped. Returns whether this lane now holds a running cluster.
 template <uint32_t S>
-DI bool lane_claim(const Dev& D, X& x, bool want) {
+DI bool cluster_claim(const Dev& D, X& x, bool want) {
   bool held = false;
   for (uint64_t wm = __ballot(want); wm; wm = __ballot(want)) {
     const uint32_t first = (uint32_t)__builtin_ctzll(wm);
@@ -2086,12 +2118,97 @@ DI bool lane_claim(const Dev& D, X& x, bool want) {
         want = false;
         x.code = MR_PASS;  // nothing left: the lane idles
       } else {
-        lane_load<S>(D, x);
+        cluster_load<S>(D, x);
         if (x.code == RUN) { held = true; want = false; }
       }
     }
   }
   return held;
+}
+// a launch begins: thread t of block b is lane b * (lanes per block) + t of the launch and starts
+// with cluster c0 + lane of the launch's chunk or, in a later launch of a streaming batch, with
+// one the previous launch's lanes still held (then the claim pointer). Returns whether it holds
+// a running cluster (its state in registers / LDS).
+template <uint32_t S>
+DI bool launch_begin(const Dev& D, X& x) {
+  // step_kernel: lanes 0 .. lpw - 1 of each 64-lane block hold clusters (D.lpw < 64: a batch
+  // smaller than the resident lanes still spreads over two waves per SIMD; the other lanes idle);
+  // pool_kernel: as many slots of each of the pool's waves
+  const uint32_t lpb = D.lpw * (MR_POOL ? POOL_WAVES : 1u);
+  x.c = blockIdx.x * lpb + threadIdx.x;
+  const bool lane_ok = threadIdx.x < lpb && x.c < D.L;
+  bool in;
+  if (D.stream && D.resume) {
+    in = lane_ok && x.c < D.nheld;
+    if (in) x.c = D.held_in[x.c];
+  } else {
+    x.c += D.c0;
+    in = lane_ok && x.c < D.C;
+  }
+  x.code = MR_PASS;
+  if (in) cluster_load<S>(D, x);
+  bool held = x.code == RUN;
+  if (D.stream) held = held || cluster_claim<S>(D, x, (D.resume ? lane_ok : in) && !held);
+  return held;
+}
+// a launch ends for a held cluster: back to HBM; still running: counted, and (streaming) resumed
+// first by the next launch
+template <uint32_t S>
+DI void launch_end(const Dev& D, X& x) {
+  cluster_store<S>(D, x);
+  if (x.code == RUN) {
+    const uint32_t k = atomicAdd(D.remaining, 1u);
+    if (D.stream) D.held_out[k] = x.c;
+  }
+}
+
+// a message key's destination bits: the Raft pool's 32-bit keys keep 3 (servers only) below the
+// AppendEntries / RequestVote bits its kinds read
+constexpr uint32_t KEY_DST = MR_POOL == 1 ? 7u : 31u;
+// the cluster's next event: the minimum (time, class, tie) key over the tester wake-up, the
+// earliest spawned thread (tcli), the node timers and the earliest message
+template <uint32_t S>
+DI void next_event(const X& x, uint64_t& key, uint32_t& cls, uint32_t& node, bool& tcli) {
+  key = ((uint64_t)x.twake << 32) | (2ull << 30);
+  cls = CLS_TESTER;
+  node = 0;
+  tcli = false;
+  if constexpr (nthr(S) > 0) {  // the earliest spawned thread (tie = tid)
+    const uint64_t kc = ((uint64_t)x.cwake << 32) | (2ull << 30) | x.ctid;
+    tcli = kc < key;
+    if (tcli) key = kc;
+  }
+#pragma unroll
+  for (uint32_t d = 0; d < NB; d++) {  // timers of absent nodes are INF_T
+    const uint64_t kt = ((uint64_t)x.timer[d] << 32) | (1ull << 30) | d;
+    if (kt < key) { key = kt; cls = CLS_TIMER; node = d; }
+  }
+  if (x.mmin < key) { key = x.mmin; cls = CLS_MSG; node = (uint32_t)key & KEY_DST; }
+}
+// the event next_event chose runs (seq: a 64-bit message key's sequence number)
+template <uint32_t S>
+DI void run_event(const Dev& D, X& x, uint64_t key, uint32_t cls, uint32_t node, bool tcli,
+                  uint32_t seq) {
+  if (nthr(S) > 0 && (uint32_t)(key >> 32) == INF_T) {  // nothing can wake the test body
+    fail(D, x, MR_FAIL_SIM_BAD_PROGRAM);
+    return;
+  }
+  x.now = (uint32_t)(key >> 32);
+  x.events++;
+  if (x.events > D.max_events) { fail(D, x, MR_FAIL_SIM_EVENT_LIMIT); return; }
+  if (cls != CLS_TESTER) {
+    CADD(cls == CLS_MSG ? CNT_EV_MSG : CNT_EV_TIMER, 1u);
+    node_event<S>(D, x, cls == CLS_MSG, node, x.mslot, seq);
+  } else {
+    CADD(CNT_EV_TESTER, 1u);
+    if constexpr (nthr(S) > 0) {
+      if (tcli) thr_step<S>(D, x, x.cslot);
+      else tester<S>(D, x);
+    } else {
+      tester<S>(D, x);
+    }
+    PROF(P_TESTER);
+  }
 }
 
 // waves per SIMD the register allocation targets: the kvraft / shard_ctrler kernels keep 64
@@ -2105,13 +2222,12 @@ constexpr uint32_t step_waves() {
 }
 // exact-size instances (NB < 8, mr_dev.h has_exact): the node count is NB at compile time
 constexpr bool EXACT_N = MR_NB < MR_MAX_NODES;
-template <uint32_t S, uint32_t NBT>
-__global__ void __launch_bounds__(STEP_BLOCK, step_waves<S>()) step_kernel(Dev Din, uint32_t budget) {
-  static_assert(NBT == NB, "one node bound per translation unit");
-  Dev D = Din;
+// configuration the scenario and the instance fix (mr_host.cpp sets the same values):
+// compile-time in the kernels, so no loop-invariant predicate on them is kept in scalar registers
+// across their loops
+template <uint32_t S>
+DI void fix_scenario(Dev& D) {
   if constexpr (EXACT_N) D.n = NB;  // the host launches this instance for D.n == NB only
-  // configuration the scenario fixes (mr_host.cpp sets the same values): compile-time here, so no
-  // loop-invariant predicate on them is kept in scalar registers across the step loop
   D.nthr = nthr(S);
   D.links = kv_gen(S).part ? 1u : 0u;
   D.lin15 = kv_gen(S).lin ? 1u : 0u;
@@ -2119,29 +2235,20 @@ __global__ void __launch_bounds__(STEP_BLOCK, step_waves<S>()) step_kernel(Dev D
   if constexpr (kv_gen(S).maxraft == 0) D.kvs32 = nullptr;
   if constexpr (is_svc(S)) __builtin_assume(D.kv32 != nullptr);
   if constexpr (kv_gen(S).maxraft > 0) __builtin_assume(D.kvs32 != nullptr);
+}
+template <uint32_t S, uint32_t NBT>
+__global__ void __launch_bounds__(STEP_BLOCK, step_waves<S>()) step_kernel(Dev Din, uint32_t budget) {
+  static_assert(NBT == NB, "one node bound per translation unit");
+  Dev D = Din;
+  fix_scenario<S>(D);
   X x;
-  // lanes 0 .. lpw - 1 of each 64-lane block hold clusters (D.lpw < 64: a batch smaller than the
-  // resident lanes still spreads over two waves per SIMD; the other lanes idle)
-  x.c = blockIdx.x * D.lpw + threadIdx.x;  // this launch's lane
 #ifdef MR_PROF
   if ((threadIdx.x & 63) == 0) {
     for (uint32_t k = 0; k < 2 * P__N; k++) s_prof[threadIdx.x >> 6][k] = 0;
     s_prof[threadIdx.x >> 6][2 * P__N] = wall_clock64();
   }
 #endif
-  const bool lane_ok = threadIdx.x < D.lpw && x.c < D.L;
-  bool in;
-  if (D.stream && D.resume) {  // a later launch of a streaming batch: the clusters the previous
-    in = lane_ok && x.c < D.nheld;  // launch's lanes still held first, then the claim pointer
-    if (in) x.c = D.held_in[x.c];
-  } else {
-    x.c += D.c0;  // lane l starts with cluster c0 + l of this launch's chunk
-    in = lane_ok && x.c < D.C;
-  }
-  x.code = MR_PASS;
-  if (in) lane_load<S>(D, x);
-  bool held = x.code == RUN;  // this lane runs cluster x.c (its state is in registers / LDS)
-  if (D.stream) held = held || lane_claim<S>(D, x, (D.resume ? lane_ok : in) && !held);
+  bool held = launch_begin<S>(D, x);  // this lane runs cluster x.c
   PROF(P_PRO);
   uint64_t key = 0;
   uint32_t cls = CLS_NONE, node = 0;
@@ -2152,27 +2259,15 @@ __global__ void __launch_bounds__(STEP_BLOCK, step_waves<S>()) step_kernel(Dev D
     if (D.stream) {  // streaming lanes: the last iteration's finished clusters make way
       const bool fin = held && x.code != RUN;
       if (__ballot(fin)) {
-        if (fin) lane_store<S>(D, x);
-        const bool got = lane_claim<S>(D, x, fin);
+        if (fin) cluster_store<S>(D, x);
+        const bool got = cluster_claim<S>(D, x, fin);
         if (fin) { held = got; need = true; }
       }
     }
     const bool run = x.code == RUN;
     if (__ballot(run) == 0) break;
-    if (run && need) {  // next event: min over tester wake-up, node timers, earliest message
-      key = ((uint64_t)x.twake << 32) | (2ull << 30);
-      cls = CLS_TESTER;
-      if constexpr (nthr(S) > 0) {  // the earliest spawned thread (tie = tid)
-        const uint64_t kc = ((uint64_t)x.cwake << 32) | (2ull << 30) | x.ctid;
-        tcli = kc < key;
-        if (tcli) key = kc;
-      }
-#pragma unroll
-      for (uint32_t d = 0; d < NB; d++) {  // timers of absent nodes are INF_T
-        uint64_t kt = ((uint64_t)x.timer[d] << 32) | (1ull << 30) | d;
-        if (kt < key) { key = kt; cls = CLS_TIMER; node = d; }
-      }
-      if (x.mmin < key) { key = x.mmin; cls = CLS_MSG; node = (uint32_t)key & 31u; }
+    if (run && need) {
+      next_event<S>(x, key, cls, node, tcli);
       need = false;
     }
     // wave-uniform choice of the event class processed this iteration
@@ -2195,27 +2290,8 @@ __global__ void __launch_bounds__(STEP_BLOCK, step_waves<S>()) step_kernel(Dev D
     }
     PROF(P_SEL);
     if (!run || !mine) continue;
-    if (nthr(S) > 0 && (uint32_t)(key >> 32) == INF_T) {  // nothing can wake the test body
-      fail(D, x, MR_FAIL_SIM_BAD_PROGRAM);
-      continue;
-    }
-    x.now = (uint32_t)(key >> 32);
     need = true;
-    x.events++;
-    if (x.events > D.max_events) { fail(D, x, MR_FAIL_SIM_EVENT_LIMIT); continue; }
-    if (cls != CLS_TESTER) {
-      CADD(cls == CLS_MSG ? CNT_EV_MSG : CNT_EV_TIMER, 1u);
-      node_event<S>(D, x, cls == CLS_MSG, node, x.mslot, ((uint32_t)key & 0x3FFFFFFFu) >> 6);
-    } else {
-      CADD(CNT_EV_TESTER, 1u);
-      if constexpr (nthr(S) > 0) {
-        if (tcli) thr_step<S>(D, x, x.cslot);
-        else tester<S>(D, x);
-      } else {
-        tester<S>(D, x);
-      }
-      PROF(P_TESTER);
-    }
+    run_event<S>(D, x, key, cls, node, tcli, ((uint32_t)key & 0x3FFFFFFFu) >> 6);
   }
 #ifdef MR_PROF
   PROF(P_TAIL);
@@ -2225,12 +2301,7 @@ __global__ void __launch_bounds__(STEP_BLOCK, step_waves<S>()) step_kernel(Dev D
       atomicAdd(&D.prof[32 + k], s_prof[threadIdx.x >> 6][P__N + k]);
     }
 #endif
-  if (!held) return;
-  lane_store<S>(D, x);
-  if (x.code == RUN) {  // still running: counted, and (streaming) resumed first by the next launch
-    const uint32_t k = atomicAdd(D.remaining, 1u);
-    if (D.stream) D.held_out[k] = x.c;
-  }
+  if (held) launch_end<S>(D, x);
 }
 
 #if MR_POOL
@@ -2349,22 +2420,23 @@ hipError_t launch_reduce(const Dev& D, unsigned long long* out, uint64_t cluster
 }
 #endif  // MR_COMMON
 
+// the step kernel's dynamic LDS: the message keys, then the per-wave staging (wstg)
+constexpr size_t step_lds_bytes(uint32_t M) {
+  return (size_t)M * STEP_BLOCK * sizeof(lkey_t) + WSTG_ROWS * STEP_BLOCK * sizeof(uint32_t);
+}
 template <uint32_t S, uint32_t NBT>
 hipError_t launch_step_t(const Dev& D, uint32_t budget, hipStream_t s) {
   dim3 blk(STEP_BLOCK), grd((D.L + D.lpw - 1) / D.lpw);
-  const size_t lds = (size_t)D.M * STEP_BLOCK * sizeof(lkey_t) +  // message keys
-                    2 * MR_MAX_NODES * STEP_BLOCK * sizeof(uint32_t);  // send-loop staging
-  hipLaunchKernelGGL((step_kernel<S, NBT>), grd, blk, lds, s, D, budget);
+  hipLaunchKernelGGL((step_kernel<S, NBT>), grd, blk, step_lds_bytes(D.M), s, D, budget);
   return hipGetLastError();
 }
 // clusters the step kernel keeps resident: blocks per CU (registers, LDS for M message slots)
 // x CUs x lanes per block
 template <uint32_t S, uint32_t NBT>
 uint32_t step_capacity_t(int device, uint32_t M) {
-  const size_t lds = (size_t)M * STEP_BLOCK * sizeof(lkey_t) + 2 * MR_MAX_NODES * STEP_BLOCK * sizeof(uint32_t);
   int blocks = 0, cus = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, (const void*)step_kernel<S, NBT>, STEP_BLOCK,
-                                                   lds) != hipSuccess ||
+                                                   step_lds_bytes(M)) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
     return 0;
   return (uint32_t)blocks * (uint32_t)cus * STEP_BLOCK;

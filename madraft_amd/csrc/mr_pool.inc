@@ -12,6 +12,9 @@
 // exactly one wave), runs their events with the state in registers through the same handlers as
 // step_kernel, and publishes each cluster's next kind. A cluster runs on one lane at a time, its events in its own order, so
 // every result equals step_kernel's and the oracle's; only which lanes run together changes.
+// What the two kernels do to a cluster between HBM and registers is one piece of code
+// (mr_kernel.hip: cluster_load / cluster_store / cluster_claim, launch_begin / launch_end,
+// next_event / run_event); here are the LDS record, the kinds and the queues.
 // The modelled gain (tools/bin_sim.py, oracle traces, r04 section costs): 1.55-1.77x.
 //
 // MR_POOL 2 units build the same kernel for the kvraft / shard_ctrler test bodies: 4 waves and
@@ -196,100 +199,14 @@ DI uint32_t px_get(const PoolL& L, X& x) {  // returns the budget end (PX_EVEND)
   return r[PX_EVEND * PS];
 }
 
-// HBM <-> registers (step_kernel's lane_load / lane_store without the lane's counter sums)
+// the kind (the queue) of the cluster's next event, which next_event chose
 template <uint32_t S>
-DI void pool_fetch(const Dev& D, X& x) {
-  x.ap0 = 0u;  // (a launch never ends inside an applier continuation)
-  x.code = CS(CS_CODE);
-  if (x.code != RUN) return;
-  x.now = CS(CS_NOW); x.events = CS(CS_EVENTS); x.msgs_sent = CS(CS_MSGS);
-  x.inflight = CS(CS_INFLIGHT); x.trace_n = CS(CS_TRACEN); x.mslot = CS(CS_MSLOT);
-  x.netmode = CS(CS_NETMODE); x.t_ctr = CS(CS_TCTR);
-  x.conn = CS(CS_CONN); x.alive = CS(CS_ALIVE); x.twake = CS(CS_TWAKE); x.lmask = CS(CS_LMASK);
-#pragma unroll
-  for (uint32_t d = 0; d < NB; d++) x.timer[d] = TMR(d);
-  x.free_mask[0] = C64(C64_FREE);
-  x.digest = C64(C64_DIGEST); x.mmin = C64(C64_MMIN);
-  x.cnt[CNT_LEADERS] = CS(CS_CNT + CNT_LEADERS);
-  x.cnt[CNT_MAX_INDEX] = CS(CS_CNT + CNT_MAX_INDEX);
-  if constexpr (nthr(S) > 0) { x.cwake = CS(CS_CWAKE); x.ctid = CS(CS_CTID); x.cslot = CS(CS_CSLOT); }
-  for (uint32_t s = 0; s < key_live(D); s++) LK(s) = (lkey_t)MKEY(s);  // (the rest stay in HBM)
-  if constexpr (MR_POOL == 2) {  // the AppendEntries requests in flight (a resumed cluster)
-    x.aem = 0ull;
-    for (uint64_t occ = ~x.free_mask[0] & (D.M >= 64 ? ~0ull : (1ull << D.M) - 1ull); occ; occ &= occ - 1ull) {
-      const uint32_t s = (uint32_t)__builtin_ctzll(occ);
-      if (hdr_type(MS32(MF_HDR, s)) == M_AE_REQ) x.aem |= 1ull << s;
-    }
-  }
-  // consumed here (see lane_load): a refill inside the loop leaves no load pending into it
-  asm volatile("" ::"v"(x.now), "v"(x.events), "v"(x.msgs_sent), "v"(x.inflight), "v"(x.trace_n),
-               "v"(x.mslot), "v"(x.netmode), "v"(x.t_ctr), "v"(x.conn), "v"(x.alive), "v"(x.twake),
-               "v"(x.lmask), "v"(x.digest), "v"(x.mmin), "v"(x.free_mask[0]),
-               "v"(x.cnt[CNT_LEADERS]), "v"(x.cnt[CNT_MAX_INDEX]));
-#pragma unroll
-  for (uint32_t d = 0; d < NB; d++) asm volatile("" ::"v"(x.timer[d]));
-}
-template <uint32_t S>
-DI void pool_store(const Dev& D, X& x) {
-  CS(CS_CODE) = x.code;
-  if (x.code != RUN) CS(CS_VTIME) = x.now;
-  CS(CS_NOW) = x.now; CS(CS_EVENTS) = x.events; CS(CS_MSGS) = x.msgs_sent;
-  CS(CS_INFLIGHT) = x.inflight; CS(CS_TRACEN) = x.trace_n; CS(CS_MSLOT) = x.mslot;
-  CS(CS_NETMODE) = x.netmode; CS(CS_TCTR) = x.t_ctr;
-  CS(CS_CONN) = x.conn; CS(CS_ALIVE) = x.alive; CS(CS_TWAKE) = x.twake; CS(CS_LMASK) = x.lmask;
-#pragma unroll
-  for (uint32_t d = 0; d < NB; d++) TMR(d) = x.timer[d];
-  C64(C64_FREE) = x.free_mask[0];
-  C64(C64_DIGEST) = x.digest; C64(C64_MMIN) = x.mmin;
-  CS(CS_CNT + CNT_LEADERS) = x.cnt[CNT_LEADERS];
-  CS(CS_CNT + CNT_MAX_INDEX) = x.cnt[CNT_MAX_INDEX];
-  if constexpr (nthr(S) > 0) { CS(CS_CWAKE) = x.cwake; CS(CS_CTID) = x.ctid; CS(CS_CSLOT) = x.cslot; }
-  if (x.code != RUN) return;  // a finished cluster's messages are never read again
-  for (uint32_t s = 0; s < key_live(D); s++) MKEY(s) = LK(s) == LKEY_FREE ? ~0ull : (uint64_t)LK(s);
-}
-// streaming: the lanes that want a cluster take the next unclaimed ones (lane_claim)
-template <uint32_t S>
-DI bool pool_claim(const Dev& D, X& x, bool want) {
-  bool held = false;
-  for (uint64_t wm = __ballot(want); wm; wm = __ballot(want)) {
-    const uint32_t first = (uint32_t)__builtin_ctzll(wm);
-    uint32_t base = 0;
-    if (__lane_id() == first) base = atomicAdd(&D.remaining[1], (uint32_t)__popcll(wm));
-    base = __shfl(base, (int)first);
-    if (want) {
-      x.c = base + (uint32_t)__popcll(wm & ((1ull << __lane_id()) - 1ull));
-      if (x.c >= D.C) {
-        want = false;
-        x.code = MR_PASS;
-      } else {
-        pool_fetch<S>(D, x);
-        if (x.code == RUN) { held = true; want = false; }
-      }
-    }
-  }
-  return held;
-}
-
-// the cluster's next event (step_kernel's rule: the minimum (time, class, tie) key over the
-// tester wake-up, the node timers and the earliest message) and its bin
-template <uint32_t S>
-DI uint32_t pool_kind(const X& x, uint64_t& key, uint32_t& cls, uint32_t& node, bool& tcli) {
+DI uint32_t pool_kind(const X& x) {
   constexpr bool FINE = pool_fine_bins<S>();
-  key = ((uint64_t)x.twake << 32) | (2ull << 30);
-  cls = CLS_TESTER;
-  node = 0;
-  tcli = false;
-  if constexpr (nthr(S) > 0) {  // the earliest spawned thread (tie = tid)
-    const uint64_t kc = ((uint64_t)x.cwake << 32) | (2ull << 30) | x.ctid;
-    tcli = kc < key;
-    if (tcli) key = kc;
-  }
-#pragma unroll
-  for (uint32_t d = 0; d < NB; d++) {
-    const uint64_t kt = ((uint64_t)x.timer[d] << 32) | (1ull << 30) | d;
-    if (kt < key) { key = kt; cls = CLS_TIMER; node = d; }
-  }
-  if (x.mmin < key) { key = x.mmin; cls = CLS_MSG; node = (uint32_t)key & (MR_POOL == 2 ? 31u : 7u); }
+  uint64_t key;
+  uint32_t cls, node;
+  bool tcli;
+  next_event<S>(x, key, cls, node, tcli);
   if constexpr (ap_cont(S))
     if (x.ap0 >> 31) return PK_APPLY;  // the current event's applier continues (AP_CAP)
   if (cls == CLS_TESTER) return PK_TESTER;
@@ -346,19 +263,11 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
   static_assert(NBT == NB, "one node bound per translation unit");
   static_assert(MR_POOL == 2 ? is_svc(S) : nthr(S) == 0 && !is_svc(S),
                 "MR_POOL 1 units run Raft-only test bodies, MR_POOL 2 units the service ones");
+  static_assert(EXACT_N, "exact-size instances only (has_pool)");
   Dev D = Din;
-  D.n = NB;  // exact-size instances only (has_pool)
-  // configuration the scenario fixes, compile-time (as step_kernel)
-  D.nthr = nthr(S);
-  D.links = kv_gen(S).part ? 1u : 0u;
-  D.lin15 = kv_gen(S).lin ? 1u : 0u;
-  if constexpr (!is_svc(S)) D.kv32 = nullptr;
-  if constexpr (kv_gen(S).maxraft == 0) D.kvs32 = nullptr;
-  if constexpr (is_svc(S)) __builtin_assume(D.kv32 != nullptr);
-  if constexpr (kv_gen(S).maxraft > 0) __builtin_assume(D.kvs32 != nullptr);
+  fix_scenario<S>(D);
   const PoolL P = pool_l(D);
   const uint32_t tid = threadIdx.x, lane = lane64();
-  const uint32_t np = D.lpw * POOL_WAVES;  // clusters per pool
   X x;
 #pragma unroll
   for (uint32_t k = 0; k < CNT__N; k++) x.cnt[k] = 0u;
@@ -376,28 +285,12 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
   for (uint32_t i = tid; i < PK__N * PS; i += POOL_SLOTS) P.q[i] = ~0u;  // no lap's tag
   if (tid == 0) *P.live = 0u;
   __syncthreads();
-  {  // prologue: slot tid takes lane blockIdx.x * np + tid of this launch
+  {  // prologue: slot tid takes its lane of this launch
     x.ls = tid;
-    const uint32_t li = blockIdx.x * np + tid;
-    const bool lane_ok = tid < np && li < D.L;
-    bool in;
-    if (D.stream && D.resume) {
-      in = lane_ok && li < D.nheld;
-      if (in) x.c = D.held_in[li];
-    } else {
-      x.c = D.c0 + li;
-      in = lane_ok && x.c < D.C;
-    }
-    x.code = MR_PASS;
-    if (in) pool_fetch<S>(D, x);
-    bool held = x.code == RUN;
-    if (D.stream) held = held || pool_claim<S>(D, x, (D.resume ? lane_ok : in) && !held);
+    const bool held = launch_begin<S>(D, x);
     uint32_t kd = 0;
     if (held) {
-      uint64_t key;
-      uint32_t cls, node;
-      bool tcli;
-      kd = pool_kind<S>(x, key, cls, node, tcli);
+      kd = pool_kind<S>(x);
       px_put<S>(P, x, x.events > ~0u - budget ? ~0u : x.events + budget);
     } else {
       P.xr[PX_C * PS + tid] = PX_EMPTY;
@@ -464,28 +357,8 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
       uint64_t key;
       uint32_t cls, node;
       bool tcli;
-      pool_kind<S>(x, key, cls, node, tcli);
-      if (nthr(S) > 0 && (uint32_t)(key >> 32) == INF_T) {  // nothing can wake the test body
-        fail(D, x, MR_FAIL_SIM_BAD_PROGRAM);
-      } else {
-        x.now = (uint32_t)(key >> 32);
-        x.events++;
-        if (x.events > D.max_events) {
-          fail(D, x, MR_FAIL_SIM_EVENT_LIMIT);
-        } else if (cls != CLS_TESTER) {
-          CADD(cls == CLS_MSG ? CNT_EV_MSG : CNT_EV_TIMER, 1u);
-          node_event<S>(D, x, cls == CLS_MSG, node, x.mslot, 0u);
-        } else {
-          CADD(CNT_EV_TESTER, 1u);
-          if constexpr (nthr(S) > 0) {
-            if (tcli) thr_step<S>(D, x, x.cslot);
-            else tester<S>(D, x);
-          } else {
-            tester<S>(D, x);
-          }
-          PROF(P_TESTER);
-        }
-      }
+      next_event<S>(x, key, cls, node, tcli);
+      run_event<S>(D, x, key, cls, node, tcli, 0u);  // (32-bit keys: no sequence number)
     }
     // the cluster back to the pool: its next kind's queue, or out of the running (a verdict, or
     // the launch's budget reached: the epilogue stores it)
@@ -493,9 +366,9 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
     // (a cluster inside an applier continuation stays in the pool past the launch's budget)
     bool cont = !fin && (x.events < evend || (ap_cont(S) && (x.ap0 >> 31)));
     if (D.stream && fin) {  // streaming: the finished cluster to HBM, the slot takes the next one
-      pool_store<S>(D, x);
+      cluster_store<S>(D, x);
       const uint32_t slot = x.ls;
-      const bool got_new = pool_claim<S>(D, x, true);
+      const bool got_new = cluster_claim<S>(D, x, true);
       x.ls = slot;
       if (got_new) {
         cont = true;
@@ -506,16 +379,7 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
     } else {
       px_put<S>(P, x, evend);
     }
-    {
-      uint32_t kd = 0;
-      if (cont) {
-        uint64_t key;
-        uint32_t cls, node;
-        bool tcli;
-        kd = pool_kind<S>(x, key, cls, node, tcli);
-      }
-      pool_publish(P, cont, kd, x.ls);
-    }
+    pool_publish(P, cont, cont ? pool_kind<S>(x) : 0u, x.ls);
 #ifdef MR_PROF
     {
       const unsigned long long dt = __shfl(wall_clock64() - t_claim, 0);
@@ -553,11 +417,7 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
   x.ls = tid;
   if (P.xr[PX_C * PS + tid] != PX_EMPTY) {
     px_get<S>(P, x);
-    pool_store<S>(D, x);
-    if (x.code == RUN) {
-      const uint32_t k = atomicAdd(D.remaining, 1u);
-      if (D.stream) D.held_out[k] = x.c;
-    }
+    launch_end<S>(D, x);
   }
   __syncthreads();
   // the lanes' counter sums: reduced in LDS (64-bit), then added to the batch's pool sums

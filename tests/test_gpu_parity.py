@@ -453,6 +453,52 @@ def test_pool_workgroup_streaming_counters(hip, monkeypatch):
         assert cp[k] == cs[k], k
 
 
+@pytest.mark.parametrize("test,clusters,budget,kw,env,stream_kw", [
+    # the service pool: the AppendEntries-slot mask rebuilt at the load, and the spawned threads'
+    # scheduler key (cwake / ctid / cslot) across a store and a load
+    ("unreliable_3a", 512, 1499, {}, {}, dict(lanes=256, stream=True)),
+    # the service pool with the applier continuation, which may outlive a launch's budget
+    ("persist_partition_unreliable_linearizable_3a", 256, 2503, {}, {}, None),
+    # the 7-server pool: message keys kept in HBM survive a store and a load
+    ("snapshot_install_unreliable_2d", 512, 3001, dict(nodes=7), {"MR_KEY_ROWS": "4"}, None),
+    # the step kernel with spawned threads, resumed
+    ("unreliable_3a", 256, 1499, {}, {"MR_POOL": "0"}, None),
+])
+def test_resumed_cluster_equals_uninterrupted(hip, oracle, monkeypatch, test, clusters, budget, kw,
+                                              env, stream_kw):
+    """A cluster stored at the end of a launch and loaded by the next one (and, streaming, one
+    taken by a lane whose cluster ended) gives the uninterrupted run's verdicts, times, digests
+    and counters, on the load / store paths test_step_budget_independence and
+    test_lanes_chunks_and_streaming (the 5-server Raft pool) do not reach. Budgets: the oracle
+    runs about 6.5 K / 14.9 K / 21.8 K events per seed on the three bodies, so 5-10 launches."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    want_kernel = "step_kernel" if env.get("MR_POOL") == "0" else "pool_kernel"
+    ocode, ocnt = compare(hip, oracle, test, clusters, **kw)  # uninterrupted == the oracle
+    with hip.Batch(test, clusters, **kw) as b:
+        assert b.run()["remaining"] == 0 and b.kernel == want_kernel
+        ref, rcnt = b.verdicts(), b.counters()
+    assert np.array_equal(ref[0], ocode)
+    for more in [{}] + ([stream_kw] if stream_kw else []):
+        with hip.Batch(test, clusters, **kw, **more) as b:
+            launches = 0
+            while True:
+                st = b.run(max_events=budget)
+                launches += st["launches"]
+                if not st["remaining"]:
+                    break
+            got, cnt = b.verdicts(), b.counters()
+            assert b.kernel == want_kernel
+        assert launches >= 2  # the case resumed at least once
+        for a_, c_ in zip(ref, got):
+            assert np.array_equal(a_, c_)
+        for k in COUNTER_KEYS:
+            assert cnt[k] == rcnt[k] == ocnt[k], k
+        assert cnt["done"] == clusters
+        if "MR_KEY_ROWS" in env:  # slots past the LDS rows (keys in HBM) were used
+            assert cnt["max_inflight"] > int(env["MR_KEY_ROWS"])
+
+
 REDUCE_CHILD = r"""
 import json, sys
 from madraft_amd import sim
