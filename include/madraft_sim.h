@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MR_ABI_VERSION 5u
+#define MR_ABI_VERSION 6u
 #define MR_MAX_NODES 8u
 #define MR_MAX_MSG_SLOTS 256u
 #define MR_MAX_AE 32u
@@ -528,9 +528,31 @@ int mr_batch_get_decisions(mr_batch* b, uint32_t k, mr_decision* out, size_t cap
  * a MR_F_RECORD batch. The tables survive mr_batch_reset (docs/SEMANTICS.md §12.1). */
 int mr_batch_set_variants(mr_batch* b, const mr_decision* base, size_t n,
                           const mr_decision* edits, size_t n_edits, const uint32_t* masks);
-/* New masks for the same base and edits: the only upload of a shrinking round. An error
- * without variants set. */
+/* New masks for the same base and edits (of either kind of variant batch, with the batch's W):
+ * the only upload of a shrinking round. An error without variants set. */
 int mr_batch_set_variant_masks(mr_batch* b, const uint32_t* masks);
+/* ABI 6: a variant batch of groups (docs/SEMANTICS.md §12.2). Each group is one seed with its own
+ * base tape and edits; cluster c is a variant of group group_of[c]'s seed. */
+typedef struct mr_variant_group {
+  uint32_t seed_cluster;      /* the group's runs are runs of the seed seed_base + cluster_base + seed_cluster
+                               * (batch-relative; need not be < n_clusters); its misses draw from that seed */
+  uint32_t base_off, n_base;  /* its base tape: base[base_off .. base_off + n_base), n_base >= 1 */
+  uint32_t edit_off, n_edits; /* its edits: edits[edit_off .. +n_edits); keys must be in ITS base tape */
+} mr_variant_group;
+/* masks[c * W + j / 32] bit j % 32 = cluster c applies edit j of its group (j counts within the
+ * group's edits), W = (max over groups of n_edits + 31) / 32; masks == NULL: no cluster applies
+ * any. n_groups == 0 drops variants of either kind, as mr_batch_set_variants(.., n = 0, ..) does;
+ * tables of mr_batch_set_decisions stay. mr_batch_set_variants is the one-group case: group
+ * {0, 0, n, 0, n_edits}, group_of all 0. Misses: mr_batch_get_decisions(b, k, NULL, 0, &n).
+ * Errors, validated before anything is freed, so the batch's tables stay as they were: a duplicate
+ * key inside one group's base or edits, an edit key absent from its own group's base (another
+ * group's does not count), a bad stream, a range that overruns n or n_edits, n_base == 0, a
+ * group_of[c] >= n_groups, a MR_F_RECORD batch, more than 2^32 - 1 records. The tables survive
+ * mr_batch_reset. */
+int mr_batch_set_variant_groups(mr_batch* b, const mr_variant_group* groups, size_t n_groups,
+                                const mr_decision* base, size_t n, const mr_decision* edits,
+                                size_t n_edits, const uint32_t* group_of /* [n_clusters] */,
+                                const uint32_t* masks);
 /* One cluster of cfg (cluster_base selects the seed for misses) driven by the n decisions:
  * its per-event trace (per-node term / role / commit / applied / last / snapshot after every
  * event), its verdict and verdict time, and (misses != NULL) its draws not in `d`. */

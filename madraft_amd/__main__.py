@@ -2,7 +2,9 @@
 analogue of `MADSIM_TEST_SEED=S MADSIM_TEST_NUM=N cargo test <test>`;
 `--replay log.jsonl` plays one cluster driven by an event-level decision log
 (madraft_amd/trace.py) and prints its verdict; `--seed S --shrink` shrinks a failing seed to a
-1-minimal set of dropped (or delayed) messages (madraft_amd/shrink.py)."""
+1-minimal set of dropped (or delayed) messages (madraft_amd/shrink.py);
+`--clusters N --shrink-failures [K]` runs the N seeds and shrinks the first K failing ones in one
+variant batch of groups, one launch per ddmin round for all of them."""
 import argparse
 import json
 import time
@@ -51,6 +53,10 @@ def main():
                     help="fault kinds to shrink, comma-separated: drop, delay (default drop)")
     ap.add_argument("--shrink-tape", metavar="LOG",
                     help="with --shrink: write the minimal run's whole tape as a --replay log")
+    ap.add_argument("--shrink-failures", type=int, nargs="?", const=16, default=None, metavar="K",
+                    help="run the --clusters seeds from --seed and shrink the first K failing "
+                         "ones together (default 16; 0 = all), one JSON line per seed in --shrink's "
+                         "format and a summary line")
     a = ap.parse_args()
     flags = 0
     if a.bug:
@@ -64,21 +70,41 @@ def main():
         print(json.dumps({"code": code, "verdict": _abi.FAIL_NAMES.get(code, str(code)),
                           "time_us": tm, "events": int(tr.size), "misses": misses}))
         raise SystemExit(0 if code == _abi.MR_PASS else 1)
-    if a.shrink:
-        seed = _abi.README_SEED if a.seed is None else a.seed
-        r = shrink.shrink_seed(a.test, seed, kinds=tuple(a.shrink_kinds.split(",")), nodes=a.nodes,
-                               iters=a.iters, unreliable=a.unreliable, null_raft=a.null,
-                               safety=a.safety, flags=flags)
+    cfg_kw = dict(nodes=a.nodes, iters=a.iters, unreliable=a.unreliable, null_raft=a.null,
+                  safety=a.safety, flags=flags)
+
+    def shrunk_line(seed, r):
         # the kept decisions as --replay lines: decoded where the test's sends have one network
         # mode, else as raw draw words
         mode = net_mode(a.test, a.unreliable)
         kept = trace.events_from_decisions(r.kept, unreliable=bool(mode), raw=mode is None)
+        return json.dumps({"code": r.code, "verdict": _abi.FAIL_NAMES.get(r.code, str(r.code)),
+                           "seed": seed, "kind": r.kind, "faults_before": r.faults,
+                           "faults_after": int(r.kept.size), "rounds": r.rounds,
+                           "candidates": r.candidates, "events": int(r.trace.size), "kept": kept})
+
+    if a.shrink:
+        seed = _abi.README_SEED if a.seed is None else a.seed
+        r = shrink.shrink_seed(a.test, seed, kinds=tuple(a.shrink_kinds.split(",")), **cfg_kw)
         if a.shrink_tape:
             trace.dump_jsonl(a.shrink_tape, r.tape, raw=True)
-        print(json.dumps({"code": r.code, "verdict": _abi.FAIL_NAMES.get(r.code, str(r.code)),
-                          "seed": seed, "kind": r.kind, "faults_before": r.faults,
-                          "faults_after": int(r.kept.size), "rounds": r.rounds,
-                          "candidates": r.candidates, "events": int(r.trace.size), "kept": kept}))
+        print(shrunk_line(seed, r))
+        raise SystemExit(0)
+    if a.shrink_failures is not None:
+        # the N seeds' verdicts, then the first K failing ones shrunk together (shrink_seeds)
+        seed = _abi.README_SEED if a.seed is None else a.seed
+        with sim.Batch(a.test, a.clusters or 1, seed, **cfg_kw) as b:
+            b.run()
+            code = b.verdicts()[0]
+        failing = [seed + int(k) for k in (code != _abi.MR_PASS).nonzero()[0]]
+        chosen = failing[: a.shrink_failures] if a.shrink_failures else failing
+        res = shrink.shrink_seeds(a.test, chosen, kinds=tuple(a.shrink_kinds.split(",")), **cfg_kw)
+        done = [r for r in res.results if not isinstance(r, str)]
+        for s, r in zip(chosen, res.results):
+            print(json.dumps({"seed": s, "skipped": r}) if isinstance(r, str) else shrunk_line(s, r))
+        print(json.dumps({"seeds": int(code.size), "failing": len(failing), "shrunk": len(done),
+                          "launches": res.launches,
+                          "kept_sizes": sorted({int(r.kept.size) for r in done})}))
         raise SystemExit(0)
     t0 = time.time()
     code, _, _, cnt = sim.run_test(a.test, a.seed, a.clusters, nodes=a.nodes, iters=a.iters,

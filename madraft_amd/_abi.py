@@ -10,7 +10,7 @@ import re
 
 import numpy as np
 
-MR_ABI_VERSION = 5
+MR_ABI_VERSION = 6
 MR_MAX_NODES = 8
 MR_RUNNING = 0xFFFF
 MR_PASS = 0
@@ -158,6 +158,10 @@ DECISION_DTYPE = np.dtype([("cluster", "<u4"), ("stream", "<u2"), ("entity", "<u
                            ("w0", "<u4"), ("w1", "<u4")])
 assert DECISION_DTYPE.itemsize == 20
 LOSS_Q32 = 429496729  # floor(0.1 * 2^32), tester.rs:130
+# mr_variant_group (ABI 6): one seed of a grouped variant batch, its slices of base and edits
+VARIANT_GROUP_DTYPE = np.dtype([("seed_cluster", "<u4"), ("base_off", "<u4"), ("n_base", "<u4"),
+                                ("edit_off", "<u4"), ("n_edits", "<u4")])
+assert VARIANT_GROUP_DTYPE.itemsize == 20
 
 
 def decision_word(v, lo, hi):
@@ -179,4 +183,5 @@ EXPORTS = [
     "mr_batch_get_decisions", "mr_decision_word", "mr_replay", "mr_batch_submit", "mr_batch_finish",
     "mr_trace_digests", "mr_trace_applies", "mr_batch_kernel",  # ABI 4
     "mr_batch_set_variants", "mr_batch_set_variant_masks",  # ABI 5
+    "mr_batch_set_variant_groups",  # ABI 6
 ]

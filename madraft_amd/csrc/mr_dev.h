@@ -206,12 +206,16 @@ struct Dev {
   uint32_t* doff;   // replay: [C + 1] row offsets into dtab
   uint32_t dcap;       // record: decisions kept per cluster
   uint32_t tape_mode;  // 0 Philox, 1 replay keyed decisions, 2 Philox and record them, 3 variants
-  // variants (tape_mode 3, SEMANTICS §12.1): dtab = the one base tape [vn], sorted by key, that
-  // every cluster replays; a miss draws from seed0, cluster 0's seed, whatever the cluster
-  uint32_t* vedit;  // [vn] the base record's edit, ~0u = none
-  uint2* vwords;    // [edits] an edit's replacement words (w0, w1)
-  uint32_t* vmask;  // [C][vW] bit j of cluster c's row: c takes edit j's words
-  uint32_t vn, vW;  // base records; mask words per cluster = ceil(edits / 32)
+  // variants (tape_mode 3, SEMANTICS §12.1, §12.2): dtab = the groups' base tapes one after the
+  // other, each slice sorted by key; a cluster replays its group's slice, takes its group's edits
+  // where its mask row says so, and draws its misses from its group's seed, seed0 + seed_cluster
+  // (mr_batch_set_variants: one group, slice = the table, seed_cluster 0)
+  uint4* vdesc;     // [C] the cluster's group: {slice offset, slice records, its first edit in
+                    // vwords, seed_cluster} (one load per draw, no group_of -> groups indirection)
+  uint32_t* vedit;  // [records] the base record's edit within its group, ~0u = none
+  uint2* vwords;    // [edits] an edit's replacement words (w0, w1), the groups' one after the other
+  uint32_t* vmask;  // [C][vW] bit j of cluster c's row: c takes its group's edit j
+  uint32_t vW;      // mask words per cluster = ceil(the widest group's edits / 32)
   uint64_t* cval;   // [C][3][CHURN_VCAP]   churn clients' committed values (churn only)
   uint32_t* cidx;   // [C][3][CHURN_VCAP]   ... and the index each was seen at
   uint32_t* cfg32;  // [C][n][CFG_CAP][CFGW] shard_ctrler config stores

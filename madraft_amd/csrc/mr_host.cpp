@@ -129,7 +129,8 @@ struct mr_batch {
   uint32_t budget = 16384;  // events per cluster per launch (MR_STEP_BUDGET)
   uint4* tape = nullptr;     // keyed decisions (own allocation: set_decisions / MR_F_RECORD)
   uint32_t* doff = nullptr;  // replay: CSR row offsets of `tape` (set_decisions)
-  uint32_t* vedit = nullptr;  // variants (set_variants): `tape` = the base tape, its edit indices,
+  uint4* vdesc = nullptr;     // variants (set_variants_impl): the clusters' group descriptors,
+  uint32_t* vedit = nullptr;  // `tape` = the groups' base tapes, their edit indices,
   uint2* vwords = nullptr;    // the edits' words,
   uint32_t* vmask = nullptr;  // and the clusters' mask rows (set_variant_masks rewrites them)
   bool submitted = false;    // mr_batch_submit enqueued a step not yet finished
@@ -661,14 +662,15 @@ uint32_t mr_decision_word(uint32_t v, uint32_t lo, uint32_t hi) {
 static void drop_decisions(mr_batch* b) {
   if (b->tape) (void)hipFree(b->tape);
   if (b->doff) (void)hipFree(b->doff);
+  if (b->vdesc) (void)hipFree(b->vdesc);
   if (b->vedit) (void)hipFree(b->vedit);
   if (b->vwords) (void)hipFree(b->vwords);
   if (b->vmask) (void)hipFree(b->vmask);
   b->tape = nullptr;
   b->doff = nullptr;
-  b->vedit = nullptr; b->vwords = nullptr; b->vmask = nullptr;
+  b->vdesc = nullptr; b->vedit = nullptr; b->vwords = nullptr; b->vmask = nullptr;
   b->D.dtab = nullptr; b->D.doff = nullptr; b->D.dcap = 0; b->D.tape_mode = 0;
-  b->D.vedit = nullptr; b->D.vwords = nullptr; b->D.vmask = nullptr; b->D.vn = 0; b->D.vW = 0;
+  b->D.vdesc = nullptr; b->D.vedit = nullptr; b->D.vwords = nullptr; b->D.vmask = nullptr; b->D.vW = 0;
 }
 
 // Keyed decisions as CSR rows: every decision once (16 B each) plus C + 1 offsets, so the
@@ -730,83 +732,143 @@ int mr_batch_set_decisions(mr_batch* b, const mr_decision* d, size_t n) {
   return no_throw("decision table", [&] { return set_decisions_impl(b, d, n); });  // host staging
 }
 
-// A variant batch (madraft_sim.h mr_batch_set_variants): the base tape sorted once, each base
-// record's edit index beside it, the edits' words, and one mask row per cluster. Validated and
-// staged whole before the previous tables are dropped, like set_decisions_impl.
-static int set_variants_impl(mr_batch* b, const mr_decision* base, size_t n, const mr_decision* edits,
-                             size_t n_edits, const uint32_t* masks) {
+// A variant batch (madraft_sim.h mr_batch_set_variant_groups; mr_batch_set_variants is its
+// one-group case, group_of == nullptr = every cluster in group 0): the groups' base tapes one after
+// the other, each slice sorted once, each base record's edit index within its group beside it, the
+// edits' words in group order, one 16-B descriptor per cluster copied from its group, and one mask
+// row per cluster. Validated and staged whole before the previous tables are dropped, like
+// set_decisions_impl.
+static int set_variants_impl(mr_batch* b, const mr_variant_group* groups, size_t n_groups,
+                             const mr_decision* base, size_t n, const mr_decision* edits,
+                             size_t n_edits, const uint32_t* group_of, const uint32_t* masks) {
   const size_t C = b->D.C;
-  if (n >= (1ull << 32) || n_edits >= (1ull << 32))
+  if (n >= (1ull << 32) || n_edits >= (1ull << 32) || n_groups >= (1ull << 32))
     return set_err("too many decisions for one batch (2^32 - 1 at most)");
+  const bool many = group_of != nullptr;  // (messages name the group only where there are groups)
+  auto in_group = [&](size_t g) { return many ? " (group " + std::to_string(g) + ")" : std::string(); };
+  size_t rows = 0, words = 0, widest = 0;
+  for (size_t g = 0; g < n_groups; g++) {
+    const mr_variant_group& G = groups[g];
+    if (G.n_base == 0) return set_err("a variant group needs a base tape, n_base >= 1" + in_group(g));
+    if ((uint64_t)G.base_off + G.n_base > n) return set_err("base range overruns n" + in_group(g));
+    if ((uint64_t)G.edit_off + G.n_edits > n_edits) return set_err("edit range overruns n_edits" + in_group(g));
+    rows += G.n_base;
+    words += G.n_edits;
+    if (G.n_edits > widest) widest = G.n_edits;
+  }
+  if (rows >= (1ull << 32) || words >= (1ull << 32))
+    return set_err("too many decisions for one batch (2^32 - 1 at most)");
+  if (many)
+    for (size_t c = 0; c < C; c++)
+      if (group_of[c] >= n_groups)
+        return set_err("group_of[" + std::to_string(c) + "] = " + std::to_string(group_of[c]) +
+                       ": no such group");
   auto key_of = [](const mr_decision& r) { return make_uint2(((uint32_t)r.stream << 16) | r.entity, r.seq); };
   auto bad_stream = [](const mr_decision& r) { return r.stream < MR_DS_TESTER || r.stream > MR_DS_NET; };
-  std::vector<uint4> tab(n);
-  for (size_t i = 0; i < n; i++) {
-    if (bad_stream(base[i])) return set_err("bad decision stream");
-    const uint2 k = key_of(base[i]);
-    tab[i] = make_uint4(k.x, k.y, base[i].w0, base[i].w1);
-  }
   auto lt = [](const uint4& a, const uint4& c) { return a.x < c.x || (a.x == c.x && a.y < c.y); };
-  std::sort(tab.begin(), tab.end(), lt);
-  for (size_t k = 1; k < n; k++)
-    if (tab[k].x == tab[k - 1].x && tab[k].y == tab[k - 1].y)
-      return set_err("duplicate decision key in the base tape");
-  std::vector<uint32_t> ved(n, ~0u);
-  std::vector<uint2> vw(n_edits);
-  for (size_t j = 0; j < n_edits; j++) {
-    if (bad_stream(edits[j])) return set_err("bad decision stream (edit " + std::to_string(j) + ")");
-    const uint2 k = key_of(edits[j]);
-    auto it = std::lower_bound(tab.begin(), tab.end(), make_uint4(k.x, k.y, 0, 0), lt);
-    if (it == tab.end() || it->x != k.x || it->y != k.y)
-      return set_err("edit " + std::to_string(j) + ": its key is not in the base tape");
-    uint32_t& e = ved[it - tab.begin()];
-    if (e != ~0u) return set_err("duplicate edit key (edits " + std::to_string(e) + " and " + std::to_string(j) + ")");
-    e = (uint32_t)j;
-    vw[j] = make_uint2(edits[j].w0, edits[j].w1);
+  std::vector<uint4> tab(rows), desc(n_groups);
+  std::vector<uint32_t> ved(rows, ~0u);
+  std::vector<uint2> vw(words);
+  size_t r0 = 0, w0 = 0;  // the group's first row of tab / ved, its first edit of vw
+  for (size_t g = 0; g < n_groups; g++) {
+    const mr_variant_group& G = groups[g];
+    uint4* row = tab.data() + r0;
+    for (size_t i = 0; i < G.n_base; i++) {
+      const mr_decision& r = base[G.base_off + i];
+      if (bad_stream(r)) return set_err("bad decision stream" + in_group(g));
+      const uint2 k = key_of(r);
+      row[i] = make_uint4(k.x, k.y, r.w0, r.w1);
+    }
+    std::sort(row, row + G.n_base, lt);
+    for (size_t k = 1; k < G.n_base; k++)
+      if (row[k].x == row[k - 1].x && row[k].y == row[k - 1].y)
+        return set_err("duplicate decision key in the base tape" + in_group(g));
+    for (size_t j = 0; j < G.n_edits; j++) {
+      const mr_decision& r = edits[G.edit_off + j];
+      if (bad_stream(r)) return set_err("bad decision stream (edit " + std::to_string(j) + ")" + in_group(g));
+      const uint2 k = key_of(r);
+      const uint4* it = std::lower_bound(row, row + G.n_base, make_uint4(k.x, k.y, 0, 0), lt);
+      if (it == row + G.n_base || it->x != k.x || it->y != k.y)
+        return set_err("edit " + std::to_string(j) + ": its key is not in the base tape" + in_group(g));
+      uint32_t& e = ved[r0 + (it - row)];
+      if (e != ~0u)
+        return set_err("duplicate edit key (edits " + std::to_string(e) + " and " + std::to_string(j) + ")" +
+                       in_group(g));
+      e = (uint32_t)j;
+      vw[w0 + j] = make_uint2(r.w0, r.w1);
+    }
+    desc[g] = make_uint4((uint32_t)r0, G.n_base, (uint32_t)w0, G.seed_cluster);
+    r0 += G.n_base;
+    w0 += G.n_edits;
   }
-  const size_t W = (n_edits + 31) / 32, mw = C * W;
-  uint4* dtab = nullptr;
+  std::vector<uint4> cdesc(C);
+  for (size_t c = 0; c < C; c++) cdesc[c] = desc[many ? group_of[c] : 0];
+  const size_t W = (widest + 31) / 32, mw = C * W;
+  uint4 *dtab = nullptr, *ddesc = nullptr;
   uint32_t *dved = nullptr, *dmask = nullptr;
   uint2* dvw = nullptr;
-  hipError_t e = hipMalloc(&dtab, n * sizeof(uint4));
-  if (e == hipSuccess) e = hipMalloc(&dved, n * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&dvw, (n_edits ? n_edits : 1) * sizeof(uint2));
+  hipError_t e = hipMalloc(&dtab, rows * sizeof(uint4));
+  if (e == hipSuccess) e = hipMalloc(&ddesc, C * sizeof(uint4));
+  if (e == hipSuccess) e = hipMalloc(&dved, rows * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&dvw, (words ? words : 1) * sizeof(uint2));
   if (e == hipSuccess) e = hipMalloc(&dmask, (mw ? mw : 1) * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemcpy(dtab, tab.data(), n * sizeof(uint4), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dved, ved.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess && n_edits)
-    e = hipMemcpy(dvw, vw.data(), n_edits * sizeof(uint2), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dtab, tab.data(), rows * sizeof(uint4), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(ddesc, cdesc.data(), C * sizeof(uint4), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dved, ved.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess && words)
+    e = hipMemcpy(dvw, vw.data(), words * sizeof(uint2), hipMemcpyHostToDevice);
   if (e == hipSuccess && mw)
     e = masks ? hipMemcpy(dmask, masks, mw * sizeof(uint32_t), hipMemcpyHostToDevice)
               : hipMemset(dmask, 0, mw * sizeof(uint32_t));
   if (e != hipSuccess) {
     if (dtab) (void)hipFree(dtab);
+    if (ddesc) (void)hipFree(ddesc);
     if (dved) (void)hipFree(dved);
     if (dvw) (void)hipFree(dvw);
     if (dmask) (void)hipFree(dmask);
     return set_err(std::string("variant tables: ") + hipGetErrorString(e));
   }
   drop_decisions(b);
-  b->tape = dtab; b->vedit = dved; b->vwords = dvw; b->vmask = dmask;
-  b->D.dtab = dtab; b->D.vedit = dved; b->D.vwords = dvw; b->D.vmask = dmask;
-  b->D.vn = (uint32_t)n; b->D.vW = (uint32_t)W;
+  b->tape = dtab; b->vdesc = ddesc; b->vedit = dved; b->vwords = dvw; b->vmask = dmask;
+  b->D.dtab = dtab; b->D.vdesc = ddesc; b->D.vedit = dved; b->D.vwords = dvw; b->D.vmask = dmask;
+  b->D.vW = (uint32_t)W;
   b->D.tape_mode = 3;
+  return 0;
+}
+
+// what the two variant calls share before their tables are looked at; 1 = go on
+static int variants_enter(mr_batch* b, bool drop) {
+  if (!b) return set_err("null batch");
+  if (b->cfg.flags & MR_F_RECORD) return set_err("variants on a MR_F_RECORD batch");
+  HIPCHK(hipSetDevice(b->cfg.device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (!drop) return 1;
+  if (b->D.tape_mode == 3u) drop_decisions(b);  // (another kind of table is not a variant's to drop)
   return 0;
 }
 
 int mr_batch_set_variants(mr_batch* b, const mr_decision* base, size_t n, const mr_decision* edits,
                           size_t n_edits, const uint32_t* masks) {
-  if (!b) return set_err("null batch");
-  if (b->cfg.flags & MR_F_RECORD) return set_err("variants on a MR_F_RECORD batch");
   if (n && !base) return set_err("null decisions");
   if (n && n_edits && !edits) return set_err("null edits");
-  HIPCHK(hipSetDevice(b->cfg.device));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  if (!n) {
-    if (b->D.tape_mode == 3u) drop_decisions(b);  // (another kind of table is not a variant's to drop)
-    return 0;
-  }
-  return no_throw("variant tables", [&] { return set_variants_impl(b, base, n, edits, n_edits, masks); });
+  if (n >= (1ull << 32) || n_edits >= (1ull << 32))
+    return set_err("too many decisions for one batch (2^32 - 1 at most)");
+  if (const int rc = variants_enter(b, n == 0); rc <= 0) return rc;
+  const mr_variant_group one{0u, 0u, (uint32_t)n, 0u, (uint32_t)n_edits};
+  return no_throw("variant tables",
+                  [&] { return set_variants_impl(b, &one, 1, base, n, edits, n_edits, nullptr, masks); });
+}
+
+int mr_batch_set_variant_groups(mr_batch* b, const mr_variant_group* groups, size_t n_groups,
+                                const mr_decision* base, size_t n, const mr_decision* edits,
+                                size_t n_edits, const uint32_t* group_of, const uint32_t* masks) {
+  if (n_groups && (!groups || !group_of)) return set_err("null groups");
+  if (n_groups && n && !base) return set_err("null decisions");
+  if (n_groups && n_edits && !edits) return set_err("null edits");
+  if (const int rc = variants_enter(b, n_groups == 0); rc <= 0) return rc;
+  return no_throw("variant tables", [&] {
+    return set_variants_impl(b, groups, n_groups, base, n, edits, n_edits, group_of, masks);
+  });
 }
 
 int mr_batch_set_variant_masks(mr_batch* b, const uint32_t* masks) {
@@ -893,6 +955,7 @@ void mr_batch_destroy(mr_batch* b) {
   if (b->base) (void)hipFree(b->base);
   if (b->tape) (void)hipFree(b->tape);
   if (b->doff) (void)hipFree(b->doff);
+  if (b->vdesc) (void)hipFree(b->vdesc);
   if (b->vedit) (void)hipFree(b->vedit);
   if (b->vwords) (void)hipFree(b->vwords);
   if (b->vmask) (void)hipFree(b->vmask);

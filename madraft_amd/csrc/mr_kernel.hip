@@ -280,11 +280,12 @@ __device__ __forceinline__ uint2 philox2(uint32_t c0, uint32_t c1, uint32_t c2, 
 // the cluster's draw: counter (c0, c1, c2) = (seq, entity, stream), key = its seed
 // (SEMANTICS §2). In MR_TAPE builds with keyed decisions set (§12), replay looks the key up
 // in the cluster's sorted table (a miss takes the Philox draw and is counted), record
-// appends {key, words} in draw order, and a variant batch looks the key up in the one table
-// all clusters share, takes an edit's words where the cluster's mask says so, and draws its
-// misses from cluster 0's seed.
+// appends {key, words} in draw order, and a variant batch looks the key up in the slice of the
+// one table that the cluster's group owns, takes an edit's words where the cluster's mask says
+// so, and draws its misses from the group's seed.
 DI void philox(const Dev& D, X& x, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t& w0,
                uint32_t& w1) {
+  uint32_t sc = x.c;  // the seed's cluster: a variant's is its group's seed_cluster
   if constexpr (MR_TAPE) {
     if (D.tape_mode) {
       const uint32_t khi = (c2 << 16) | c1;
@@ -302,29 +303,32 @@ DI void philox(const Dev& D, X& x, uint32_t c0, uint32_t c1, uint32_t c2, uint32
           if (r.x == khi && r.y == c0) { w0 = r.z; w1 = r.w; return; }
         }
         CS(CS_TAPE) = CS(CS_TAPE) + 1u;  // no record: the seed's own draw
-      } else if (D.tape_mode == 3u) {  // variants (§12.1): one shared sorted table for every cluster
-        const uint4* tb = D.dtab;
-        uint32_t lo = 0, n = D.vn;
-        while (n) {  // (a wave's lanes probe the same rows until their keys part: coalesced loads)
+      } else if (D.tape_mode == 3u) {  // variants (§12.1, §12.2): the cluster's group's sorted slice
+        const uint4 g = D.vdesc[x.c];  // {slice offset, records, first edit, seed_cluster}
+        const uint4* tb = D.dtab + g.x;
+        uint32_t lo = 0, n = g.y;
+        while (n) {  // (lanes of one group probe the same rows until their keys part: coalesced
+                     // loads; slices differ in length, so the trip count is the wave's longest)
           const uint32_t h = n >> 1;
           const uint4 r = tb[lo + h];
           if (r.x < khi || (r.x == khi && r.y < c0)) { lo += h + 1; n -= h + 1; }
           else n = h;
         }
-        if (lo < D.vn) {
+        if (lo < g.y) {
           const uint4 r = tb[lo];
-          const uint32_t e = D.vedit[lo];  // the record's edit, ~0u = none (issued with r)
+          const uint32_t e = D.vedit[g.x + lo];  // the record's edit in its group, ~0u = none (issued with r)
           if (r.x == khi && r.y == c0) {
             w0 = r.z; w1 = r.w;
             if (e != ~0u) {  // the cluster's mask bit and the edit's words, loaded together
               const uint32_t m = D.vmask[(size_t)x.c * D.vW + (e >> 5)];
-              const uint2 ew = D.vwords[e];
+              const uint2 ew = D.vwords[g.z + e];
               if ((m >> (e & 31u)) & 1u) { w0 = ew.x; w1 = ew.y; }
             }
             return;
           }
         }
-        CS(CS_TAPE) = CS(CS_TAPE) + 1u;  // no record: cluster 0's seed, whatever x.c (below)
+        CS(CS_TAPE) = CS(CS_TAPE) + 1u;  // no record: the group's seed, whatever x.c (below)
+        sc = g.w;
       } else {
         uint4* tb = D.dtab + (size_t)x.c * D.dcap;
         const uint64_t seed = D.seed0 + x.c;
@@ -338,8 +342,7 @@ DI void philox(const Dev& D, X& x, uint32_t c0, uint32_t c1, uint32_t c2, uint32
       }
     }
   }
-  // every cluster of a variant batch is a run of cluster 0's seed
-  const uint64_t seed = D.seed0 + (MR_TAPE && D.tape_mode == 3u ? 0u : x.c);
+  const uint64_t seed = D.seed0 + sc;
   const uint2 w = philox2(c0, c1, c2, (uint32_t)seed, (uint32_t)(seed >> 32));
   w0 = w.x;
   w1 = w.y;
@@ -845,7 +848,8 @@ DI Dev dev_launder(const Dev& D0) {
   D.M = glu(D0.M); D.K = glu(D0.K); D.hb = glu(D0.hb); D.elo = glu(D0.elo); D.ehi = glu(D0.ehi);
   D.safety = glu(D0.safety); D.max_events = glu(D0.max_events);
   if constexpr (MR_TAPE) {  // a variant batch's tables (null otherwise)
-    D.vedit = glp(D0.vedit); D.vwords = glp(D0.vwords); D.vmask = glp(D0.vmask);
+    D.vdesc = glp(D0.vdesc); D.vedit = glp(D0.vedit); D.vwords = glp(D0.vwords);
+    D.vmask = glp(D0.vmask);
   }
   return D;
 }

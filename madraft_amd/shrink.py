@@ -5,7 +5,10 @@ long latency. An edit takes one fault away (the message is delivered, the latenc
 a candidate is the set of faults it keeps, every other fault edited away. `shrink` is delta
 debugging (ddmin, Zeller & Hildebrandt 2002) over such sets with every round's candidates
 evaluated at once; `shrink_seed` evaluates a round as one variant batch on the GPU
-(`Batch.set_variants`): one shared base tape, one mask row per candidate.
+(`Batch.set_variants`): one shared base tape, one mask row per candidate. `shrink_seeds` does
+it for many failing seeds at once (§12.2): ddmin is a resumable walk, `shrink_many` drives one
+walk per seed in lockstep, and a joint round is one run of a variant batch of groups
+(`Batch.set_variant_groups`).
 """
 import collections
 
@@ -47,6 +50,25 @@ def shrink(evaluate, n_faults, target):
 
     Returns Shrunk(kept: ascending indices, rounds: evaluate calls, candidates: rows submitted).
     """
+    return drive(shrink_walk(n_faults, target), evaluate)
+
+
+def drive(walk, evaluate):
+    """Run one resumable walk (shrink_walk, passes_walk) to its end: every array it yields goes
+    to `evaluate`, whose verdict codes it receives; the walk's return value."""
+    try:
+        rows = next(walk)
+        while True:
+            rows = walk.send(evaluate(rows))
+    except StopIteration as stop:
+        return stop.value
+
+
+def shrink_walk(n_faults, target):
+    """shrink() as a resumable walk: a generator that yields each round's keep array
+    [candidates, n_faults], is sent that round's verdict codes, and returns the Shrunk. The
+    policy is shrink()'s; who runs the candidates, and what else runs beside them, is the
+    driver's business (drive: one walk; shrink_many: one per seed, in lockstep)."""
     n = int(n_faults)
 
     def rows(sets):
@@ -55,14 +77,15 @@ def shrink(evaluate, n_faults, target):
             keep[r, s] = True
         return keep
 
-    def failing(sets):
-        codes = np.asarray(evaluate(rows(sets)))
+    def failing(sets, codes):
+        codes = np.asarray(codes)
         assert codes.shape == (len(sets),), codes.shape
         return codes == target
 
     cur = np.arange(n)
     rounds, cands = 1, 2
-    empty_fails, full_fails = failing([cur[:0], cur])
+    sets = [cur[:0], cur]
+    empty_fails, full_fails = failing(sets, (yield rows(sets)))
     if empty_fails:
         return Shrunk(cur[:0], rounds, cands)
     if not full_fails:
@@ -75,7 +98,7 @@ def shrink(evaluate, n_faults, target):
             sets += [np.concatenate(chunks[:i] + chunks[i + 1:]) for i in range(g)]
         rounds += 1
         cands += len(sets)
-        hit = np.nonzero(failing(sets))[0]
+        hit = np.nonzero(failing(sets, (yield rows(sets))))[0]
         if hit.size:
             cur = sets[hit[0]]
             g = 2 if hit[0] < len(chunks) else max(g - 1, 2)
@@ -137,19 +160,27 @@ def shrink_passes(evaluate_masks, base, kinds, target):
     Returns Passes: the kind that was shrunk last, kept (positions in the edit list of the
     faults that stay), applied (the minimal run's edits), that kind's faults before, evaluate
     calls and candidates over all passes, and the edit list's idx and edits."""
+    return drive(passes_walk(base, kinds, target), evaluate_masks)
+
+
+def passes_walk(base, kinds, target):
+    """shrink_passes() as a resumable walk: yields each round's applied array [candidates,
+    n_edits], is sent its verdict codes, returns the Passes."""
     idx, edits, kind_of = edit_list(base, kinds)
     fixed = np.zeros(idx.size, bool)  # edits applied in every candidate of the pass
     rounds = cands = 0
     order = [k for k in KINDS if k in kinds]
     for kind in order:
         mine = np.nonzero(kind_of == kind)[0]
-
-        def evaluate(keep):
-            applied = np.tile(fixed, (keep.shape[0], 1))
-            applied[:, mine] = ~keep
-            return evaluate_masks(applied)
-
-        res = shrink(evaluate, mine.size, target)
+        walk = shrink_walk(mine.size, target)
+        try:
+            keep = next(walk)
+            while True:
+                applied = np.tile(fixed, (keep.shape[0], 1))
+                applied[:, mine] = ~keep
+                keep = walk.send((yield applied))
+        except StopIteration as stop:
+            res = stop.value
         rounds += res.rounds
         cands += res.candidates
         fixed[mine] = True  # (a kind that is not the cause stays edited away in the next pass)
@@ -157,6 +188,34 @@ def shrink_passes(evaluate_masks, base, kinds, target):
             applied = fixed.copy()
             applied[mine[res.kept]] = False
             return Passes(kind, mine[res.kept], applied, mine.size, rounds, cands, idx, edits)
+
+
+def shrink_many(evaluate_groups, bases, kinds, targets):
+    """shrink_passes for several seeds at once: one walk per seed (bases[g], targets[g]), driven
+    in lockstep. Each round the live walks' candidates go to one call of
+    `evaluate_groups({g: applied[candidates, n_edits of g]}) -> {g: codes}`; a walk that has
+    finished is given nothing more. Every walk sees only its own verdicts, so the Passes of seed
+    g is what shrink_passes returns for it alone, and the number of evaluate_groups calls is the
+    largest rounds among them.
+
+    Returns (list of Passes, evaluate_groups calls)."""
+    walks = [passes_walk(b, kinds, t) for b, t in zip(bases, targets)]
+    out = [None] * len(walks)
+    rows = {}
+    for g, w in enumerate(walks):
+        rows[g] = next(w)  # (every walk has a first round: the empty and the full set)
+    calls = 0
+    while rows:
+        codes = evaluate_groups(rows)
+        calls += 1
+        nxt = {}
+        for g in rows:
+            try:
+                nxt[g] = walks[g].send(np.asarray(codes[g]))
+            except StopIteration as stop:
+                out[g] = stop.value
+        rows = nxt
+    return out, calls
 
 
 def n_variants(base, kinds):
@@ -209,3 +268,86 @@ def shrink_seed(test, seed, kinds=("drop",), tape_cap=1 << 16, **cfg_kw):
         raise sim.SimError(f"the minimal tape replays to verdict {code}, not {target}")
     return ShrunkSeed(base[p.idx[p.kept]], p.kind, target, tr, tape, p.faults, p.rounds,
                       p.candidates)
+
+
+SeedsShrunk = collections.namedtuple("SeedsShrunk", "results launches")
+
+
+def shrink_seeds(test, seeds, kinds=("drop",), tape_cap=1 << 16, **cfg_kw):
+    """shrink_seed for every seed of `seeds` at once (docs/SEMANTICS.md §12.2): each seed is
+    recorded (one 1-cluster MR_F_RECORD batch, reset to seed after seed), then one variant batch
+    holds a group per failing seed — group g owns a contiguous run of n_variants(its base, kinds)
+    clusters — and every round of shrink_many is one set_variant_masks + reset + run of it: the
+    launches are the longest seed's rounds, not their sum. A finished group's clusters repeat its
+    candidate 0 and their verdicts are ignored. Each minimal tape is replayed (mr_replay) and
+    must give the seed's verdict, as in shrink_seed.
+
+    Returns SeedsShrunk(results, launches): results[i] is the ShrunkSeed of seeds[i], or, for a
+    seed that is not shrunk, the string "passes" or "tape_cap" (it drew more than tape_cap
+    decisions); launches = runs of the variant batch."""
+    from . import sim
+    seeds = [int(s) for s in seeds]
+    flags = int(cfg_kw.pop("flags", 0))
+    base_c = int(cfg_kw.pop("cluster_base", 0))
+    results = [None] * len(seeds)
+    if not seeds:
+        return SeedsShrunk(results, 0)
+    seed_base = seeds[0] - base_c  # the variant batch's; group g's seed_cluster = its seed - seeds[0]
+    if min(seeds) < seeds[0] or max(seeds) - seeds[0] >= 1 << 32:
+        raise sim.SimError("shrink_seeds: seeds[0] must be the smallest, the others within 2^32 of it")
+    live, bases, targets = [], [], []
+    with sim.Batch(test, 1, seed_base, cluster_base=base_c, flags=flags | _abi.MR_F_RECORD,
+                   tape_cap=tape_cap, **cfg_kw) as b:
+        for i, s in enumerate(seeds):
+            b.reset(s - base_c)
+            b.run()
+            code = int(b.verdicts()[0][0])
+            n, base = b.decisions(0, tape_cap)
+            if code == _abi.MR_PASS or n > tape_cap:
+                results[i] = "passes" if code == _abi.MR_PASS else "tape_cap"
+                continue
+            live.append(i)
+            bases.append(base.copy())
+            targets.append(code)
+    if not live:
+        return SeedsShrunk(results, 0)
+    lists = [edit_list(bs, kinds) for bs in bases]
+    width = [n_variants(bs, kinds) for bs in bases]
+    first = np.cumsum([0] + width)  # group g's clusters: first[g] .. first[g + 1]
+    clusters, n_edits = int(first[-1]), max(ls[1].size for ls in lists)
+    launches = 0
+    with sim.Batch(test, clusters, seed_base, cluster_base=base_c, flags=flags, **cfg_kw) as b:
+        b.set_variant_groups([(seeds[i] - seeds[0], bs, ls[1])
+                              for i, bs, ls in zip(live, bases, lists)],
+                             np.repeat(np.arange(len(live)), width))
+        masks = np.zeros((clusters, n_edits), bool)
+
+        def evaluate_groups(rows):
+            nonlocal launches
+            for g in range(len(live)):
+                m = masks[first[g]: first[g + 1]]
+                if g in rows:
+                    applied = rows[g]
+                    m[: applied.shape[0], : applied.shape[1]] = applied
+                    m[applied.shape[0]:] = m[0]
+                else:  # finished: candidate 0 of its last round in every row
+                    m[1:] = m[0]
+            b.set_variant_masks(masks)
+            b.reset(seed_base)
+            st = b.run()
+            assert st["remaining"] == 0, st
+            launches += 1
+            code = b.verdicts()[0]
+            return {g: code[first[g]: first[g] + applied.shape[0]] for g, applied in rows.items()}
+
+        passes, _ = shrink_many(evaluate_groups, bases, kinds, targets)
+    for i, bs, target, p in zip(live, bases, targets, passes):
+        tape = apply_edits(bs, p.idx, p.edits, p.applied)
+        tr, code, _, _ = sim.replay(test, tape, seed=seeds[i] - base_c, cluster_base=base_c,
+                                    flags=flags, **cfg_kw)
+        if code != target:
+            raise sim.SimError(f"seed {seeds[i]}: the minimal tape replays to verdict {code}, "
+                               f"not {target}")
+        results[i] = ShrunkSeed(bs[p.idx[p.kept]], p.kind, target, tr, tape, p.faults, p.rounds,
+                                p.candidates)
+    return SeedsShrunk(results, launches)

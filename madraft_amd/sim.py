@@ -60,6 +60,9 @@ def lib():
     L.mr_batch_set_variants.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.c_size_t, C.c_void_p]
     L.mr_batch_set_variant_masks.argtypes = [C.c_void_p, C.c_void_p]
+    L.mr_batch_set_variant_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_void_p]
     L.mr_decision_word.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     L.mr_decision_word.restype = C.c_uint32
     L.mr_replay.argtypes = [C.POINTER(MrCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
@@ -239,8 +242,42 @@ class Batch:
                                            m.ctypes.data if m is not None and m.size else None))
         self._n_edits = int(e.size)
 
+    def set_variant_groups(self, groups, group_of, masks=None):
+        """Make cluster c a variant of group group_of[c]'s seed (mr_batch_set_variant_groups;
+        SEMANTICS §12.2). `groups` is a list of (seed_cluster, base, edits): the group's runs are
+        runs of the seed seed_base + cluster_base + seed_cluster, replay its `base` decisions and
+        apply `edits` (None: none) of it; `masks` [clusters, max_edits] bool, or packed uint32
+        rows, column j = edit j of the cluster's own group (max_edits = the widest group's edits;
+        None: no cluster applies any). No groups = Philox again."""
+        if groups is None or len(groups) == 0:
+            _check(lib().mr_batch_set_variant_groups(self._b, None, 0, None, 0, None, 0, None,
+                                                     None))
+            self._n_edits = 0
+            return
+        bases = [np.ascontiguousarray(b, dtype=DECISION_DTYPE).ravel() for _, b, _ in groups]
+        edits = [np.ascontiguousarray(e if e is not None else [], dtype=DECISION_DTYPE).ravel()
+                 for _, _, e in groups]
+        g = np.zeros(len(groups), _abi.VARIANT_GROUP_DTYPE)
+        g["seed_cluster"] = [int(s) for s, _, _ in groups]
+        g["n_base"] = [b.size for b in bases]
+        g["n_edits"] = [e.size for e in edits]
+        g["base_off"] = np.cumsum(g["n_base"], dtype=np.uint64) - g["n_base"]
+        g["edit_off"] = np.cumsum(g["n_edits"], dtype=np.uint64) - g["n_edits"]
+        a, e = np.concatenate(bases), np.concatenate(edits)
+        of = np.ascontiguousarray(group_of, dtype=np.uint32)
+        if of.shape != (self.clusters,):
+            raise SimError(f"group_of: shape {of.shape}, not ({self.clusters},)")
+        widest = int(g["n_edits"].max())
+        m = self._mask_words(masks, widest)
+        _check(lib().mr_batch_set_variant_groups(
+            self._b, g.ctypes.data, g.size, a.ctypes.data if a.size else None, a.size,
+            e.ctypes.data if e.size else None, e.size, of.ctypes.data,
+            m.ctypes.data if m is not None and m.size else None))
+        self._n_edits = widest
+
     def set_variant_masks(self, masks):
-        """New masks for the variants set (mr_batch_set_variant_masks); then reset() and run()."""
+        """New masks for the variants set (mr_batch_set_variant_masks), [clusters, edits] bool or
+        packed rows (a grouped batch: edits = the widest group's); then reset() and run()."""
         m = self._mask_words(masks, self._n_edits)
         _check(lib().mr_batch_set_variant_masks(self._b, m.ctypes.data if m is not None and m.size
                                                 else None))
