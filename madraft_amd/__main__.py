@@ -83,28 +83,29 @@ def main():
                            "faults_after": int(r.kept.size), "rounds": r.rounds,
                            "candidates": r.candidates, "events": int(r.trace.size), "kept": kept})
 
-    if a.shrink:
+    if a.shrink or a.shrink_failures is not None:
+        # --shrink: the seed itself; else the N seeds' verdicts and the first K failing ones.
+        # Either way the chosen seeds are shrunk together (shrink_seeds)
         seed = _abi.README_SEED if a.seed is None else a.seed
-        r = shrink.shrink_seed(a.test, seed, kinds=tuple(a.shrink_kinds.split(",")), **cfg_kw)
-        if a.shrink_tape:
-            trace.dump_jsonl(a.shrink_tape, r.tape, raw=True)
-        print(shrunk_line(seed, r))
-        raise SystemExit(0)
-    if a.shrink_failures is not None:
-        # the N seeds' verdicts, then the first K failing ones shrunk together (shrink_seeds)
-        seed = _abi.README_SEED if a.seed is None else a.seed
-        with sim.Batch(a.test, a.clusters or 1, seed, **cfg_kw) as b:
-            b.run()
-            code = b.verdicts()[0]
-        failing = [seed + int(k) for k in (code != _abi.MR_PASS).nonzero()[0]]
-        chosen = failing[: a.shrink_failures] if a.shrink_failures else failing
+        chosen = [seed]
+        if not a.shrink:
+            with sim.Batch(a.test, a.clusters or 1, seed, **cfg_kw) as b:
+                b.run()
+                code = b.verdicts()[0]
+            failing = [seed + int(k) for k in (code != _abi.MR_PASS).nonzero()[0]]
+            chosen = failing[: a.shrink_failures] if a.shrink_failures else failing
         res = shrink.shrink_seeds(a.test, chosen, kinds=tuple(a.shrink_kinds.split(",")), **cfg_kw)
         done = [r for r in res.results if not isinstance(r, str)]
+        if a.shrink and not done:
+            raise sim.SimError(res.results[0].error)
+        if a.shrink and a.shrink_tape:
+            trace.dump_jsonl(a.shrink_tape, done[0].tape, raw=True)
         for s, r in zip(chosen, res.results):
             print(json.dumps({"seed": s, "skipped": r}) if isinstance(r, str) else shrunk_line(s, r))
-        print(json.dumps({"seeds": int(code.size), "failing": len(failing), "shrunk": len(done),
-                          "launches": res.launches,
-                          "kept_sizes": sorted({int(r.kept.size) for r in done})}))
+        if not a.shrink:
+            print(json.dumps({"seeds": int(code.size), "failing": len(failing), "shrunk": len(done),
+                              "launches": res.launches,
+                              "kept_sizes": sorted({int(r.kept.size) for r in done})}))
         raise SystemExit(0)
     t0 = time.time()
     code, _, _, cnt = sim.run_test(a.test, a.seed, a.clusters, nodes=a.nodes, iters=a.iters,

@@ -110,6 +110,35 @@ int set_err(const std::string& s) {
   } while (0)
 
 constexpr uint32_t STEP_LANES = 64;  // lanes per step-kernel block (one wave)
+
+// A batch's decision tables on the device, each its own allocation, whoever made them: replay
+// rows and offsets (set_decisions_impl), the record tape (MR_F_RECORD), or a variant batch's base
+// tapes, descriptors, edits and masks (set_variants_impl). All null: Philox draws.
+struct Tables {
+  uint4* tape = nullptr;      // keyed decisions: replay rows, the record tape, the groups' base tapes
+  uint32_t* doff = nullptr;   // replay: CSR row offsets of `tape`
+  uint4* vdesc = nullptr;     // variants: the clusters' group descriptors,
+  uint32_t* vedit = nullptr;  // the base records' edit indices within their group,
+  uint2* vwords = nullptr;    // the edits' words,
+  uint32_t* vmask = nullptr;  // and the clusters' mask rows (set_variant_masks rewrites them)
+  uint32_t dcap = 0, vW = 0, mode = 0;  // Dev's dcap, vW and tape_mode with these tables
+};
+
+void free_tables(Tables& t) {
+  for (void* p : {(void*)t.tape, (void*)t.doff, (void*)t.vdesc, (void*)t.vedit, (void*)t.vwords,
+                  (void*)t.vmask})
+    if (p) (void)hipFree(p);
+  t = Tables{};
+}
+
+// *dst = a new device array of max(count, 1) elements: src[0 .. count), or zeros for a null src
+template <class T>
+hipError_t upload(T** dst, const T* src, size_t count) {
+  const hipError_t e = hipMalloc(dst, (count ? count : 1) * sizeof(T));
+  if (e != hipSuccess || !count) return e;
+  return src ? hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice)
+             : hipMemset(*dst, 0, count * sizeof(T));
+}
 }  // namespace
 
 struct mr_batch {
@@ -127,12 +156,7 @@ struct mr_batch {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   uint32_t budget = 16384;  // events per cluster per launch (MR_STEP_BUDGET)
-  uint4* tape = nullptr;     // keyed decisions (own allocation: set_decisions / MR_F_RECORD)
-  uint32_t* doff = nullptr;  // replay: CSR row offsets of `tape` (set_decisions)
-  uint4* vdesc = nullptr;     // variants (set_variants_impl): the clusters' group descriptors,
-  uint32_t* vedit = nullptr;  // `tape` = the groups' base tapes, their edit indices,
-  uint2* vwords = nullptr;    // the edits' words,
-  uint32_t* vmask = nullptr;  // and the clusters' mask rows (set_variant_masks rewrites them)
+  Tables dec;                // the decision tables D draws from (install_tables)
   bool submitted = false;    // mr_batch_submit enqueued a step not yet finished
   uint32_t kern = 0;         // kernel family of the launches since the reset: 1 pool, 2 step / tape
   std::chrono::steady_clock::time_point t_submit;
@@ -148,6 +172,17 @@ static int copy_trace_row(mr_batch* b, uint32_t k, const T* rows, T* out, size_t
   HIPCHK(hipMemcpy(out, rows + (size_t)k * b->D.trace_cap, m * sizeof(T), hipMemcpyDeviceToHost));
   *n = m;
   return 0;
+}
+
+// `t` (staged whole by the caller) becomes the batch's decision tables, the previous ones are
+// freed, and the kernels' view of them is published into D
+static void install_tables(mr_batch* b, const Tables& t) {
+  free_tables(b->dec);
+  b->dec = t;
+  Dev& D = b->D;
+  D.dtab = t.tape; D.doff = t.doff; D.dcap = t.dcap;
+  D.vdesc = t.vdesc; D.vedit = t.vedit; D.vwords = t.vwords; D.vmask = t.vmask; D.vW = t.vW;
+  D.tape_mode = t.mode;
 }
 
 // A C entry point whose host allocations may throw: an error code across the C ABI, never an
@@ -319,14 +354,15 @@ static int mr_batch_create_impl(const mr_cfg* cfg, mr_batch** out) {
     p += (it.bytes + 255) & ~size_t(255);
   }
   if (cfg->flags & MR_F_RECORD) {
-    e = hipMalloc(&b->tape, (size_t)C * cfg->tape_cap * sizeof(uint4));
+    Tables t;  // (the tape is written before it is read: not filled)
+    e = hipMalloc(&t.tape, (size_t)C * cfg->tape_cap * sizeof(uint4));
     if (e != hipSuccess) {
       mr_batch_destroy(b);
       return set_err(std::string("tape allocation failed: ") + hipGetErrorString(e));
     }
-    b->D.dtab = b->tape;
-    b->D.dcap = cfg->tape_cap;
-    b->D.tape_mode = 2;
+    t.dcap = cfg->tape_cap;
+    t.mode = 2;
+    install_tables(b, t);
   }
   if (hipMemset(b->D.prof, 0, PROF_SLOTS * sizeof(unsigned long long)) != hipSuccess ||
       hipMemset(b->D.guard, 0, 4 * sizeof(uint32_t)) != hipSuccess) {
@@ -659,18 +695,17 @@ uint32_t mr_decision_word(uint32_t v, uint32_t lo, uint32_t hi) {
 
 // the batch's decision tables (replay rows + offsets, the record tape, or a variant batch's
 // base tape, edits and masks) freed; Philox draws
-static void drop_decisions(mr_batch* b) {
-  if (b->tape) (void)hipFree(b->tape);
-  if (b->doff) (void)hipFree(b->doff);
-  if (b->vdesc) (void)hipFree(b->vdesc);
-  if (b->vedit) (void)hipFree(b->vedit);
-  if (b->vwords) (void)hipFree(b->vwords);
-  if (b->vmask) (void)hipFree(b->vmask);
-  b->tape = nullptr;
-  b->doff = nullptr;
-  b->vdesc = nullptr; b->vedit = nullptr; b->vwords = nullptr; b->vmask = nullptr;
-  b->D.dtab = nullptr; b->D.doff = nullptr; b->D.dcap = 0; b->D.tape_mode = 0;
-  b->D.vdesc = nullptr; b->D.vedit = nullptr; b->D.vwords = nullptr; b->D.vmask = nullptr; b->D.vW = 0;
+static void drop_decisions(mr_batch* b) { install_tables(b, Tables{}); }
+
+// `t`, staged by a chain of upload()s that ended with `e`: installed, or on an error freed, the
+// batch keeping its previous tables (`what` names them in the message)
+static int install_staged(mr_batch* b, Tables& t, hipError_t e, const char* what) {
+  if (e != hipSuccess) {
+    free_tables(t);
+    return set_err(std::string(what) + ": " + hipGetErrorString(e));
+  }
+  install_tables(b, t);
+  return 0;
 }
 
 // Keyed decisions as CSR rows: every decision once (16 B each) plus C + 1 offsets, so the
@@ -701,26 +736,11 @@ static int set_decisions_impl(mr_batch* b, const mr_decision* d, size_t n) {
       if (row[k].x == row[k - 1].x && row[k].y == row[k - 1].y)
         return set_err("duplicate decision key (cluster " + std::to_string(c) + ")");
   }
-  uint4* dtab = nullptr;
-  uint32_t* doff = nullptr;
-  hipError_t e = hipMalloc(&dtab, (n ? n : 1) * sizeof(uint4));
-  if (e == hipSuccess) e = hipMalloc(&doff, off.size() * sizeof(uint32_t));
-  if (e == hipSuccess && n)
-    e = hipMemcpy(dtab, tab.data(), n * sizeof(uint4), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy(doff, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (dtab) (void)hipFree(dtab);
-    if (doff) (void)hipFree(doff);
-    return set_err(std::string("decision table: ") + hipGetErrorString(e));
-  }
-  drop_decisions(b);
-  b->tape = dtab;
-  b->doff = doff;
-  b->D.dtab = dtab;
-  b->D.doff = doff;
-  b->D.tape_mode = 1;
-  return 0;
+  Tables t;
+  t.mode = 1;
+  hipError_t e = upload(&t.tape, tab.data(), n);
+  if (e == hipSuccess) e = upload(&t.doff, off.data(), off.size());
+  return install_staged(b, t, e, "decision table");
 }
 
 int mr_batch_set_decisions(mr_batch* b, const mr_decision* d, size_t n) {
@@ -804,36 +824,15 @@ static int set_variants_impl(mr_batch* b, const mr_variant_group* groups, size_t
   std::vector<uint4> cdesc(C);
   for (size_t c = 0; c < C; c++) cdesc[c] = desc[many ? group_of[c] : 0];
   const size_t W = (widest + 31) / 32, mw = C * W;
-  uint4 *dtab = nullptr, *ddesc = nullptr;
-  uint32_t *dved = nullptr, *dmask = nullptr;
-  uint2* dvw = nullptr;
-  hipError_t e = hipMalloc(&dtab, rows * sizeof(uint4));
-  if (e == hipSuccess) e = hipMalloc(&ddesc, C * sizeof(uint4));
-  if (e == hipSuccess) e = hipMalloc(&dved, rows * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&dvw, (words ? words : 1) * sizeof(uint2));
-  if (e == hipSuccess) e = hipMalloc(&dmask, (mw ? mw : 1) * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemcpy(dtab, tab.data(), rows * sizeof(uint4), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(ddesc, cdesc.data(), C * sizeof(uint4), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dved, ved.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess && words)
-    e = hipMemcpy(dvw, vw.data(), words * sizeof(uint2), hipMemcpyHostToDevice);
-  if (e == hipSuccess && mw)
-    e = masks ? hipMemcpy(dmask, masks, mw * sizeof(uint32_t), hipMemcpyHostToDevice)
-              : hipMemset(dmask, 0, mw * sizeof(uint32_t));
-  if (e != hipSuccess) {
-    if (dtab) (void)hipFree(dtab);
-    if (ddesc) (void)hipFree(ddesc);
-    if (dved) (void)hipFree(dved);
-    if (dvw) (void)hipFree(dvw);
-    if (dmask) (void)hipFree(dmask);
-    return set_err(std::string("variant tables: ") + hipGetErrorString(e));
-  }
-  drop_decisions(b);
-  b->tape = dtab; b->vdesc = ddesc; b->vedit = dved; b->vwords = dvw; b->vmask = dmask;
-  b->D.dtab = dtab; b->D.vdesc = ddesc; b->D.vedit = dved; b->D.vwords = dvw; b->D.vmask = dmask;
-  b->D.vW = (uint32_t)W;
-  b->D.tape_mode = 3;
-  return 0;
+  Tables t;
+  t.vW = (uint32_t)W;
+  t.mode = 3;
+  hipError_t e = upload(&t.tape, tab.data(), rows);
+  if (e == hipSuccess) e = upload(&t.vdesc, cdesc.data(), C);
+  if (e == hipSuccess) e = upload(&t.vedit, ved.data(), rows);
+  if (e == hipSuccess) e = upload(&t.vwords, vw.data(), words);
+  if (e == hipSuccess) e = upload(&t.vmask, masks, mw);
+  return install_staged(b, t, e, "variant tables");
 }
 
 // what the two variant calls share before their tables are looked at; 1 = go on
@@ -878,8 +877,8 @@ int mr_batch_set_variant_masks(mr_batch* b, const uint32_t* masks) {
   HIPCHK(hipStreamSynchronize(b->stream));
   const size_t mw = (size_t)b->D.C * b->D.vW;
   if (!mw) return 0;
-  if (masks) HIPCHK(hipMemcpy(b->vmask, masks, mw * sizeof(uint32_t), hipMemcpyHostToDevice));
-  else HIPCHK(hipMemset(b->vmask, 0, mw * sizeof(uint32_t)));
+  if (masks) HIPCHK(hipMemcpy(b->dec.vmask, masks, mw * sizeof(uint32_t), hipMemcpyHostToDevice));
+  else HIPCHK(hipMemset(b->dec.vmask, 0, mw * sizeof(uint32_t)));
   return 0;
 }
 
@@ -896,7 +895,7 @@ static int mr_batch_get_decisions_impl(mr_batch* b, uint32_t k, mr_decision* out
   if (m > cap) m = cap;
   std::vector<uint4> rows(m);
   if (m)
-    HIPCHK(hipMemcpy(rows.data(), b->tape + (size_t)k * b->D.dcap, m * sizeof(uint4),
+    HIPCHK(hipMemcpy(rows.data(), b->dec.tape + (size_t)k * b->D.dcap, m * sizeof(uint4),
                      hipMemcpyDeviceToHost));
   for (size_t i = 0; i < m; i++)
     out[i] = mr_decision{k, (uint16_t)(rows[i].x >> 16), (uint16_t)(rows[i].x & 0xFFFFu), rows[i].y,
@@ -953,12 +952,7 @@ void mr_batch_destroy(mr_batch* b) {
   }
 #endif
   if (b->base) (void)hipFree(b->base);
-  if (b->tape) (void)hipFree(b->tape);
-  if (b->doff) (void)hipFree(b->doff);
-  if (b->vdesc) (void)hipFree(b->vdesc);
-  if (b->vedit) (void)hipFree(b->vedit);
-  if (b->vwords) (void)hipFree(b->vwords);
-  if (b->vmask) (void)hipFree(b->vmask);
+  free_tables(b->dec);
   // the streaming held-cluster lists belong to the batch, not to its decision tables
   for (uint32_t h = 0; h < 2; h++)
     if (b->held[h]) { (void)hipFree(b->held[h]); b->held[h] = nullptr; }

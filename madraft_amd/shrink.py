@@ -4,11 +4,10 @@ A recorded run is a set of keyed decisions. Some of them are faults: a dropped m
 long latency. An edit takes one fault away (the message is delivered, the latency is 1 ms);
 a candidate is the set of faults it keeps, every other fault edited away. `shrink` is delta
 debugging (ddmin, Zeller & Hildebrandt 2002) over such sets with every round's candidates
-evaluated at once; `shrink_seed` evaluates a round as one variant batch on the GPU
-(`Batch.set_variants`): one shared base tape, one mask row per candidate. `shrink_seeds` does
-it for many failing seeds at once (§12.2): ddmin is a resumable walk, `shrink_many` drives one
-walk per seed in lockstep, and a joint round is one run of a variant batch of groups
-(`Batch.set_variant_groups`).
+evaluated at once. ddmin is a resumable walk; `shrink_many` drives one walk per failing seed in
+lockstep, and `shrink_seeds` evaluates a joint round as one run of a variant batch of groups on
+the GPU (`Batch.set_variant_groups`, §12.2): per seed one base tape and one mask row per
+candidate. `shrink_seed` is its one-seed case.
 """
 import collections
 
@@ -56,12 +55,19 @@ def shrink(evaluate, n_faults, target):
 def drive(walk, evaluate):
     """Run one resumable walk (shrink_walk, passes_walk) to its end: every array it yields goes
     to `evaluate`, whose verdict codes it receives; the walk's return value."""
+    rows, done = _advance(walk)
+    while rows is not None:
+        rows, done = _advance(walk, evaluate(rows))
+    return done
+
+
+def _advance(walk, codes=None):
+    """One step of a resumable walk: started (codes None) or sent its last round's verdict codes,
+    it gives (its next round's rows, None), or at its end (None, its return value)."""
     try:
-        rows = next(walk)
-        while True:
-            rows = walk.send(evaluate(rows))
+        return walk.send(codes), None
     except StopIteration as stop:
-        return stop.value
+        return None, stop.value
 
 
 def shrink_walk(n_faults, target):
@@ -173,14 +179,11 @@ def passes_walk(base, kinds, target):
     for kind in order:
         mine = np.nonzero(kind_of == kind)[0]
         walk = shrink_walk(mine.size, target)
-        try:
-            keep = next(walk)
-            while True:
-                applied = np.tile(fixed, (keep.shape[0], 1))
-                applied[:, mine] = ~keep
-                keep = walk.send((yield applied))
-        except StopIteration as stop:
-            res = stop.value
+        keep, res = _advance(walk)
+        while keep is not None:
+            applied = np.tile(fixed, (keep.shape[0], 1))
+            applied[:, mine] = ~keep
+            keep, res = _advance(walk, (yield applied))
         rounds += res.rounds
         cands += res.candidates
         fixed[mine] = True  # (a kind that is not the cause stays edited away in the next pass)
@@ -201,20 +204,16 @@ def shrink_many(evaluate_groups, bases, kinds, targets):
     Returns (list of Passes, evaluate_groups calls)."""
     walks = [passes_walk(b, kinds, t) for b, t in zip(bases, targets)]
     out = [None] * len(walks)
-    rows = {}
-    for g, w in enumerate(walks):
-        rows[g] = next(w)  # (every walk has a first round: the empty and the full set)
+    # (every walk has a first round: the empty and the full set)
+    rows = {g: _advance(w)[0] for g, w in enumerate(walks)}
     calls = 0
     while rows:
         codes = evaluate_groups(rows)
         calls += 1
         nxt = {}
         for g in rows:
-            try:
-                nxt[g] = walks[g].send(np.asarray(codes[g]))
-            except StopIteration as stop:
-                out[g] = stop.value
-        rows = nxt
+            nxt[g], out[g] = _advance(walks[g], np.asarray(codes[g]))
+        rows = {g: r for g, r in nxt.items() if r is not None}
     return out, calls
 
 
@@ -225,66 +224,48 @@ def n_variants(base, kinds):
 
 def shrink_seed(test, seed, kinds=("drop",), tape_cap=1 << 16, **cfg_kw):
     """Shrink the failing run of `test` at `seed` (make_cfg's keywords: iters, flags, ...) to a
-    1-minimal set of faults of `kinds` on the GPU: the seed is recorded (MR_F_RECORD, one
-    cluster), then every ddmin round is one run of one variant batch whose masks are the
-    round's candidates (unused clusters repeat candidate 0).
+    1-minimal set of faults of `kinds` on the GPU: shrink_seeds' one-seed case — one record run,
+    one variant batch of n_variants(base, kinds) clusters, one launch per ddmin round, one
+    mr_replay of the minimal tape. A seed that passes, or draws more than tape_cap decisions, is a
+    SimError.
 
     Returns ShrunkSeed: kept (the base records of the faults that stay, DECISION_DTYPE), their
     kind, the verdict code, the minimal run's trace (mr_replay of its tape), that tape, the
     faults of that kind before, evaluate rounds and candidates run."""
     from . import sim
-    flags = int(cfg_kw.pop("flags", 0))
-    base_c = int(cfg_kw.pop("cluster_base", 0))
-    seed_base = int(seed) - base_c  # cluster 0's seed (seed_base + cluster_base) is `seed`
-    with sim.Batch(test, 1, seed_base, cluster_base=base_c, flags=flags | _abi.MR_F_RECORD,
-                   tape_cap=tape_cap, **cfg_kw) as b:
-        b.run()
-        target = int(b.verdicts()[0][0])
-        n, base = b.decisions(0, tape_cap)
-    if n > tape_cap:
-        raise sim.SimError(f"tape_cap {tape_cap} too small: the seed draws {n} decisions")
-    if target == _abi.MR_PASS:
-        raise sim.SimError(f"seed {seed} passes {test}: nothing to shrink")
-    base = base.copy()
-    clusters = n_variants(base, kinds)
-    with sim.Batch(test, clusters, seed_base, cluster_base=base_c, flags=flags, **cfg_kw) as b:
-        b.set_variants(base, edit_list(base, kinds)[1])
-
-        def evaluate_masks(applied):
-            m = np.empty((clusters, applied.shape[1]), bool)
-            m[: applied.shape[0]] = applied
-            m[applied.shape[0]:] = applied[0]
-            b.set_variant_masks(m)
-            b.reset(seed_base)
-            st = b.run()
-            assert st["remaining"] == 0, st
-            return b.verdicts()[0][: applied.shape[0]]
-
-        p = shrink_passes(evaluate_masks, base, kinds, target)
-    tape = apply_edits(base, p.idx, p.edits, p.applied)
-    tr, code, _, _ = sim.replay(test, tape, seed=seed_base, cluster_base=base_c, flags=flags,
-                                **cfg_kw)
-    if code != target:
-        raise sim.SimError(f"the minimal tape replays to verdict {code}, not {target}")
-    return ShrunkSeed(base[p.idx[p.kept]], p.kind, target, tr, tape, p.faults, p.rounds,
-                      p.candidates)
+    r = shrink_seeds(test, [seed], kinds, tape_cap, **cfg_kw).results[0]
+    if isinstance(r, str):
+        raise sim.SimError(r.error)
+    return r
 
 
 SeedsShrunk = collections.namedtuple("SeedsShrunk", "results launches")
 
 
+class NotShrunk(str):
+    """Why shrink_seeds left a seed alone, "passes" or "tape_cap": a str, with `error`, what
+    shrink_seed says of that seed."""
+
+    def __new__(cls, why, error):
+        self = super().__new__(cls, why)
+        self.error = error
+        return self
+
+
 def shrink_seeds(test, seeds, kinds=("drop",), tape_cap=1 << 16, **cfg_kw):
-    """shrink_seed for every seed of `seeds` at once (docs/SEMANTICS.md §12.2): each seed is
-    recorded (one 1-cluster MR_F_RECORD batch, reset to seed after seed), then one variant batch
-    holds a group per failing seed — group g owns a contiguous run of n_variants(its base, kinds)
-    clusters — and every round of shrink_many is one set_variant_masks + reset + run of it: the
-    launches are the longest seed's rounds, not their sum. A finished group's clusters repeat its
+    """Shrink the failing runs of `test` at every seed of `seeds` at once (docs/SEMANTICS.md
+    §12.2; make_cfg's keywords: iters, flags, ...), each to a 1-minimal set of faults of `kinds`:
+    each seed is recorded (one 1-cluster MR_F_RECORD batch, reset to seed after seed), then one
+    variant batch holds a group per failing seed — group g owns a contiguous run of
+    n_variants(its base, kinds) clusters — and every round of shrink_many is one
+    set_variant_masks + reset + run of it: the launches are the longest seed's rounds, not their
+    sum. The clusters a group's round does not use, and all of a finished group's, repeat its
     candidate 0 and their verdicts are ignored. Each minimal tape is replayed (mr_replay) and
-    must give the seed's verdict, as in shrink_seed.
+    must give the seed's verdict.
 
     Returns SeedsShrunk(results, launches): results[i] is the ShrunkSeed of seeds[i], or, for a
-    seed that is not shrunk, the string "passes" or "tape_cap" (it drew more than tape_cap
-    decisions); launches = runs of the variant batch."""
+    seed that is not shrunk, the string (NotShrunk) "passes" or "tape_cap" (it drew more than
+    tape_cap decisions); launches = runs of the variant batch."""
     from . import sim
     seeds = [int(s) for s in seeds]
     flags = int(cfg_kw.pop("flags", 0))
@@ -299,12 +280,16 @@ def shrink_seeds(test, seeds, kinds=("drop",), tape_cap=1 << 16, **cfg_kw):
     with sim.Batch(test, 1, seed_base, cluster_base=base_c, flags=flags | _abi.MR_F_RECORD,
                    tape_cap=tape_cap, **cfg_kw) as b:
         for i, s in enumerate(seeds):
-            b.reset(s - base_c)
+            if i:  # (the batch starts at seeds[0])
+                b.reset(s - base_c)
             b.run()
             code = int(b.verdicts()[0][0])
             n, base = b.decisions(0, tape_cap)
             if code == _abi.MR_PASS or n > tape_cap:
-                results[i] = "passes" if code == _abi.MR_PASS else "tape_cap"
+                results[i] = NotShrunk(
+                    "passes" if code == _abi.MR_PASS else "tape_cap",
+                    f"tape_cap {tape_cap} too small: the seed draws {n} decisions" if n > tape_cap
+                    else f"seed {s} passes {test}: nothing to shrink")
                 continue
             live.append(i)
             bases.append(base.copy())

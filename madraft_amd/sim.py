@@ -135,6 +135,18 @@ def make_cfg(test, clusters=1, seed=_abi.README_SEED, *, nodes=None, iters=0, un
     return cfg
 
 
+def _ptr(a):
+    """The address of array `a` for a C call; NULL for None or an empty array."""
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def _records(d):
+    """(array, its _ptr) of keyed decisions for a C call: `d` (records or None) as one flat
+    contiguous DECISION_DTYPE array."""
+    a = np.ascontiguousarray(d if d is not None else [], dtype=DECISION_DTYPE).ravel()
+    return a, _ptr(a)
+
+
 class Batch:
     """`clusters` seeds of one reference test, resident on one GPU."""
 
@@ -196,16 +208,17 @@ class Batch:
         _check(lib().mr_batch_counters(self._b, C.byref(c)))
         return c.to_dict()
 
+    def _set_tables(self, rc, n_edits=0):
+        """After a call that replaces or drops the decision tables: `n_edits` = the mask columns
+        of the variants now set (0: none; any earlier variants went with the tables)."""
+        _check(rc)
+        self._n_edits = int(n_edits)
+
     def set_decisions(self, d):
         """Drive the clusters by keyed decisions (DECISION_DTYPE records, any order;
         SEMANTICS §12); None = Philox again. Call before run()."""
-        if d is None or len(d) == 0:
-            _check(lib().mr_batch_set_decisions(self._b, None, 0))
-            self._n_edits = 0  # (any variants are dropped with the tables)
-            return
-        a = np.ascontiguousarray(d, dtype=DECISION_DTYPE)
-        _check(lib().mr_batch_set_decisions(self._b, a.ctypes.data, a.size))
-        self._n_edits = 0
+        a, pa = _records(d)
+        self._set_tables(lib().mr_batch_set_decisions(self._b, pa, a.size))
 
     def _mask_words(self, masks, n_edits):
         """[clusters, ceil(n_edits / 32)] uint32 mask rows from a bool array [clusters, n_edits]
@@ -230,17 +243,11 @@ class Batch:
         §12.1): `base` decisions shared by all, `edits` that replace the words of base records,
         `masks` [clusters, len(edits)] bool (or packed uint32 rows) saying which cluster applies
         which edit (None: none). base None or empty = Philox again."""
-        if base is None or len(base) == 0:
-            _check(lib().mr_batch_set_variants(self._b, None, 0, None, 0, None))
-            self._n_edits = 0
-            return
-        a = np.ascontiguousarray(base, dtype=DECISION_DTYPE)
-        e = np.ascontiguousarray(edits if edits is not None else [], dtype=DECISION_DTYPE)
-        m = self._mask_words(masks, e.size)
-        _check(lib().mr_batch_set_variants(self._b, a.ctypes.data, a.size,
-                                           e.ctypes.data if e.size else None, e.size,
-                                           m.ctypes.data if m is not None and m.size else None))
-        self._n_edits = int(e.size)
+        a, pa = _records(base)
+        e, pe = _records(edits if a.size else None)
+        m = self._mask_words(masks if a.size else None, e.size)
+        self._set_tables(lib().mr_batch_set_variants(self._b, pa, a.size, pe, e.size, _ptr(m)),
+                         e.size)
 
     def set_variant_groups(self, groups, group_of, masks=None):
         """Make cluster c a variant of group group_of[c]'s seed (mr_batch_set_variant_groups;
@@ -249,38 +256,30 @@ class Batch:
         apply `edits` (None: none) of it; `masks` [clusters, max_edits] bool, or packed uint32
         rows, column j = edit j of the cluster's own group (max_edits = the widest group's edits;
         None: no cluster applies any). No groups = Philox again."""
-        if groups is None or len(groups) == 0:
-            _check(lib().mr_batch_set_variant_groups(self._b, None, 0, None, 0, None, 0, None,
-                                                     None))
-            self._n_edits = 0
-            return
-        bases = [np.ascontiguousarray(b, dtype=DECISION_DTYPE).ravel() for _, b, _ in groups]
-        edits = [np.ascontiguousarray(e if e is not None else [], dtype=DECISION_DTYPE).ravel()
-                 for _, _, e in groups]
+        groups = [(int(s), _records(b)[0], _records(e)[0]) for s, b, e in groups or []]
         g = np.zeros(len(groups), _abi.VARIANT_GROUP_DTYPE)
-        g["seed_cluster"] = [int(s) for s, _, _ in groups]
-        g["n_base"] = [b.size for b in bases]
-        g["n_edits"] = [e.size for e in edits]
+        g["seed_cluster"] = [s for s, _, _ in groups]
+        g["n_base"] = [b.size for _, b, _ in groups]
+        g["n_edits"] = [e.size for _, _, e in groups]
         g["base_off"] = np.cumsum(g["n_base"], dtype=np.uint64) - g["n_base"]
         g["edit_off"] = np.cumsum(g["n_edits"], dtype=np.uint64) - g["n_edits"]
-        a, e = np.concatenate(bases), np.concatenate(edits)
-        of = np.ascontiguousarray(group_of, dtype=np.uint32)
-        if of.shape != (self.clusters,):
-            raise SimError(f"group_of: shape {of.shape}, not ({self.clusters},)")
-        widest = int(g["n_edits"].max())
-        m = self._mask_words(masks, widest)
-        _check(lib().mr_batch_set_variant_groups(
-            self._b, g.ctypes.data, g.size, a.ctypes.data if a.size else None, a.size,
-            e.ctypes.data if e.size else None, e.size, of.ctypes.data,
-            m.ctypes.data if m is not None and m.size else None))
-        self._n_edits = widest
+        a, pa = _records(np.concatenate([b for _, b, _ in groups]) if groups else None)
+        e, pe = _records(np.concatenate([e for _, _, e in groups]) if groups else None)
+        widest = int(g["n_edits"].max(initial=0))
+        of = m = None
+        if groups:
+            of = np.ascontiguousarray(group_of, dtype=np.uint32)
+            if of.shape != (self.clusters,):
+                raise SimError(f"group_of: shape {of.shape}, not ({self.clusters},)")
+            m = self._mask_words(masks, widest)
+        self._set_tables(lib().mr_batch_set_variant_groups(
+            self._b, _ptr(g), g.size, pa, a.size, pe, e.size, _ptr(of), _ptr(m)), widest)
 
     def set_variant_masks(self, masks):
         """New masks for the variants set (mr_batch_set_variant_masks), [clusters, edits] bool or
         packed rows (a grouped batch: edits = the widest group's); then reset() and run()."""
         m = self._mask_words(masks, self._n_edits)
-        _check(lib().mr_batch_set_variant_masks(self._b, m.ctypes.data if m is not None and m.size
-                                                else None))
+        _check(lib().mr_batch_set_variant_masks(self._b, _ptr(m)))
 
     def decisions(self, k, cap=1 << 20):
         """(n, records): with MR_F_RECORD cluster k's decisions in draw order (n drawn);
@@ -324,10 +323,10 @@ def replay(test, decisions, trace_cap=1 << 16, cluster_base=0, **kw):
     """mr_replay: one cluster of `test` driven by keyed decisions (DECISION_DTYPE records,
     any order): (per-event trace, verdict code, verdict time, draws without a record)."""
     cfg = make_cfg(test, 1, cluster_base=cluster_base, **kw)
-    d = np.ascontiguousarray(decisions, dtype=DECISION_DTYPE)
+    d, pd = _records(decisions)
     out = np.empty(trace_cap, EVENT_DTYPE)
     n, code, tm, ms = C.c_size_t(), C.c_uint16(), C.c_uint32(), C.c_uint64()
-    _check(lib().mr_replay(C.byref(cfg), d.ctypes.data if d.size else None, d.size,
+    _check(lib().mr_replay(C.byref(cfg), pd, d.size,
                            out.ctypes.data, trace_cap, C.byref(n), C.byref(code), C.byref(tm),
                            C.byref(ms)))
     return out[: n.value], int(code.value), int(tm.value), int(ms.value)

@@ -13,7 +13,6 @@ import numpy as np
 import pytest
 
 from madraft_amd import _abi, shrink
-from tests import variant_groups_util as vg
 from tests import variants_util as vu
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +31,7 @@ SEED = _abi.README_SEED
 @functools.lru_cache(maxsize=None)
 def _group(k):
     """(base, idx, edits) of seed k with every recorded drop as an edit."""
-    base = vg.recorded(k)[0]
+    base = vu.recorded(vu.NAME, k)[0]
     idx, edits = shrink.find_edits(base, "drop")
     return base, idx, edits
 
@@ -87,11 +86,11 @@ def _groups(shuffle=False):
 
 
 def _want(group_of, applied):
-    return [vg.variant(SEEDS[g], a) for g, a in zip(group_of, applied)]
+    return [vu.variant(vu.NAME, vu.KINDS, a, SEEDS[g]) for g, a in zip(group_of, applied)]
 
 
 def _batch(hip, clusters, **kw):
-    test, ckw = vu.FIXTURES[vg.NAME]
+    test, ckw = vu.FIXTURES[vu.NAME]
     return hip.Batch(test, clusters, **ckw, **kw)
 
 
@@ -134,7 +133,8 @@ def test_every_variant_equals_the_oracles_replay_at_its_groups_seed(hip, layout)
     for c in range(traced):  # per-node state after every event, record for record
         k = SEEDS[group_of[c]]
         base, idx, edits = _group(k)
-        otr = vg.replay(k, shrink.apply_edits(base, idx, edits, applied[c]), trace_cap=TRACE_CAP)[4]
+        otr = vu.replay(vu.NAME, shrink.apply_edits(base, idx, edits, applied[c]), k,
+                        trace_cap=TRACE_CAP)[4]
         assert np.array_equal(tr[c], otr), c
 
 
@@ -151,9 +151,9 @@ def test_a_miss_draws_from_the_groups_own_seed(hip):
         b.run()
         got = _results(b)
     for c, r in enumerate(got):
-        assert r[:3] == vg.plain(SEEDS[group_of[c]]), c
+        assert r[:3] == vu.plain(vu.NAME, SEEDS[group_of[c]]), c
         assert r[3] > 0, c
-    assert len({vg.plain(k)[2] for k in SEEDS}) == 4
+    assert len({vu.plain(vu.NAME, k)[2] for k in SEEDS}) == 4
 
 
 def test_one_group_equals_set_variants(hip):
@@ -303,7 +303,7 @@ def test_rejected_groups_leave_the_previous_tables_working(hip):
         b.reset(SEED)
         b.run()
         assert _results(b) == want
-    test, ckw = vu.FIXTURES[vg.NAME]
+    test, ckw = vu.FIXTURES[vu.NAME]
     ckw = dict(ckw, flags=ckw["flags"] | _abi.MR_F_RECORD)
     with hip.Batch(test, 2, tape_cap=vu.CAP, **ckw) as b:
         with pytest.raises(hip.SimError, match="MR_F_RECORD"):
@@ -314,26 +314,26 @@ def test_rejected_groups_leave_the_previous_tables_working(hip):
 
 
 def test_shrink_seeds_walks_the_oracles_ddmin_for_every_seed(hip):
-    test, ckw = vu.FIXTURES[vg.NAME]
-    seeds = [SEED + k for k in vg.SEEDS]
-    res, launches = shrink.shrink_seeds(test, seeds, kinds=vg.KINDS, **ckw)
-    alone = [vg.oracle_passes(k) for k in vg.SEEDS]
-    for k, r, p in zip(vg.SEEDS, res, alone):
-        base, code, _ = vg.recorded(k)
+    test, ckw = vu.FIXTURES[vu.NAME]
+    seeds = [SEED + k for k in vu.SEEDS]
+    res, launches = shrink.shrink_seeds(test, seeds, kinds=vu.KINDS, **ckw)
+    alone = [vu.oracle_passes(vu.NAME, vu.KINDS, k) for k in vu.SEEDS]
+    for k, r, p in zip(vu.SEEDS, res, alone):
+        base, code, _ = vu.recorded(vu.NAME, k)
         assert r.code == code and r.kind == p.kind and r.faults == p.faults, k
         assert (r.rounds, r.candidates) == (p.rounds, p.candidates), k
         assert np.array_equal(r.kept, base[p.idx[p.kept]]), k
         tape = shrink.apply_edits(base, p.idx, p.edits, p.applied)
         assert np.array_equal(r.tape, tape), k
-        assert np.array_equal(r.trace, vg.replay(k, tape, trace_cap=TRACE_CAP)[4]), k
+        assert np.array_equal(r.trace, vu.replay(vu.NAME, tape, k, trace_cap=TRACE_CAP)[4]), k
     assert launches == max(p.rounds for p in alone)
     assert launches < sum(p.rounds for p in alone)  # one seed at a time: a launch per round each
 
 
 def test_shrink_seeds_reports_seeds_it_does_not_shrink(hip):
-    test, ckw = vu.FIXTURES[vg.NAME]
-    assert vg.plain(1)[0] == 0 and vg.recorded(0)[0].size > 64
-    res, launches = shrink.shrink_seeds(test, [SEED, SEED + 1], kinds=vg.KINDS, tape_cap=64, **ckw)
+    test, ckw = vu.FIXTURES[vu.NAME]
+    assert vu.plain(vu.NAME, 1)[0] == 0 and vu.recorded(vu.NAME, 0)[0].size > 64
+    res, launches = shrink.shrink_seeds(test, [SEED, SEED + 1], kinds=vu.KINDS, tape_cap=64, **ckw)
     assert res == ["tape_cap", "passes"] and launches == 0
 
 

@@ -196,6 +196,31 @@ def test_shrink_seed_walks_the_oracles_ddmin(hip, name, kinds):
     assert np.array_equal(r.trace, otr)
 
 
+def test_shrink_seed_is_shrink_seeds_of_one_seed(hip):
+    test, ckw = vu.FIXTURES["many_election"]
+    kinds = ("drop", "delay")
+    base = vu.recorded("many_election")[0]
+    assert base.size == 50 and shrink.find_edits(base, "drop")[0].size == 3
+    one = shrink.shrink_seed(test, _abi.README_SEED, kinds=kinds, **ckw)
+    res, launches = shrink.shrink_seeds(test, [_abi.README_SEED], kinds=kinds, **ckw)
+    assert len(res) == 1 and isinstance(res[0], shrink.ShrunkSeed)
+    for field, x, y in zip(shrink.ShrunkSeed._fields, one, res[0]):
+        assert np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y, field
+    assert launches == one.rounds  # one launch per ddmin round
+
+
+def test_shrink_seed_raises_for_a_seed_it_does_not_shrink(hip):
+    test, ckw = vu.FIXTURES["figure_8"]
+    seed = _abi.README_SEED
+    n = vu.recorded("figure_8")[0].size
+    assert vu.plain("figure_8", 1)[0] == 0 and n > 64  # by the oracle: seed + 1 passes
+    with pytest.raises(hip.SimError, match=f"^seed {seed + 1} passes {test}: nothing to shrink$"):
+        shrink.shrink_seed(test, seed + 1, **ckw)
+    with pytest.raises(hip.SimError,
+                       match=f"^tape_cap 64 too small: the seed draws {n} decisions$"):
+        shrink.shrink_seed(test, seed, tape_cap=64, **ckw)
+
+
 def test_cli_shrink_output_replays_to_the_same_verdict(hip, tmp_path):
     p = vu.oracle_passes("figure_8", ("drop",))
     base = vu.recorded("figure_8")[0]

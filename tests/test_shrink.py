@@ -99,3 +99,33 @@ def test_oracle_many_election_fails_without_drops_then_shrinks_delays():
     assert p.kind == "delay" and p.applied[:3].all()  # every drop delivered
     assert p.faults == shrink.find_edits(base, "delay")[0].size
     vu.assert_one_minimal("many_election", p)
+
+
+def test_merged_helper_at_seed_0_is_the_cluster_0_fixture():
+    """The helpers take a seed index k and run seed k with cluster_base = k. At k = 0 that is
+    what they did before they took one: cluster 0 of a config whose cluster_base is left at its
+    default, every candidate replayed directly (no memo)."""
+    o = vu.oracle()
+    test, ckw = vu.FIXTURES["figure_8"]
+    cfg = o.cfg(test, **ckw)
+    with o.recording(1, vu.CAP) as (count, rec):
+        code = int(o.run_batch(cfg, 0, 1)[0][0])
+    base = rec[0, : int(count[0])].copy()
+    idx, edits, _ = shrink.edit_list(base, ("drop",))
+
+    def evaluate_masks(applied):
+        out = []
+        for a in applied:
+            with o.replaying(shrink.apply_edits(base, idx, edits, a), 1):
+                out.append(int(o.run_batch(cfg, 0, 1)[0][0]))
+        return np.array(out)
+
+    q = shrink.shrink_passes(evaluate_masks, base, ("drop",), code)
+    p = vu.oracle_passes("figure_8", ("drop",), k=0)
+    assert np.array_equal(vu.recorded("figure_8", 0)[0], base)
+    assert vu.recorded("figure_8", 0)[1] == code == 43
+    assert p.faults == q.faults == 87 and p.kind == q.kind == "drop"
+    assert np.array_equal(p.kept, q.kept) and np.array_equal(p.applied, q.applied)
+    assert (p.rounds, p.candidates) == (q.rounds, q.candidates)
+    assert np.array_equal(p.idx, q.idx) and np.array_equal(p.edits, q.edits)
+    assert np.array_equal(vu.oracle_passes("figure_8", ("drop",)).kept, p.kept)  # k left out

@@ -5,35 +5,35 @@ is given nothing more."""
 import numpy as np
 
 from madraft_amd import shrink
-from tests import variant_groups_util as vg
+from tests import variants_util as vu
 
 
 def _joint():
-    """shrink_many over the oracle evaluators of vg.SEEDS: (passes, calls, the groups of every
+    """shrink_many over the oracle evaluators of vu.SEEDS: (passes, calls, the groups of every
     evaluate_groups call, the candidates of every per-seed evaluation)."""
-    rounds, counts = [], {g: [] for g in range(len(vg.SEEDS))}
-    evals = [vg.evaluator(k, counts[g]) for g, k in enumerate(vg.SEEDS)]
+    rounds, counts = [], {g: [] for g in range(len(vu.SEEDS))}
+    evals = [vu.evaluator(vu.NAME, vu.KINDS, k, counts[g]) for g, k in enumerate(vu.SEEDS)]
 
     def evaluate_groups(rows):
         rounds.append(sorted(rows))
         return {g: evals[g](applied) for g, applied in rows.items()}
 
-    bases = [vg.recorded(k)[0] for k in vg.SEEDS]
-    targets = [vg.recorded(k)[1] for k in vg.SEEDS]
-    passes, calls = shrink.shrink_many(evaluate_groups, bases, vg.KINDS, targets)
+    bases = [vu.recorded(vu.NAME, k)[0] for k in vu.SEEDS]
+    targets = [vu.recorded(vu.NAME, k)[1] for k in vu.SEEDS]
+    passes, calls = shrink.shrink_many(evaluate_groups, bases, vu.KINDS, targets)
     return passes, calls, rounds, counts
 
 
 def test_the_fixture_seeds_fail_and_differ_in_rounds():
-    alone = [vg.oracle_passes(k) for k in vg.SEEDS]
-    assert all(vg.recorded(k)[1] != 0 for k in vg.SEEDS)
+    alone = [vu.oracle_passes(vu.NAME, vu.KINDS, k) for k in vu.SEEDS]
+    assert all(vu.recorded(vu.NAME, k)[1] != 0 for k in vu.SEEDS)
     assert len({p.rounds for p in alone}) > 2  # long, short and one-round walks side by side
     assert min(p.rounds for p in alone) == 1 and max(p.rounds for p in alone) > 8
 
 
 def test_shrink_many_gives_each_seed_the_passes_of_shrinking_it_alone():
     passes, calls, rounds, counts = _joint()
-    alone = [vg.oracle_passes(k) for k in vg.SEEDS]
+    alone = [vu.oracle_passes(vu.NAME, vu.KINDS, k) for k in vu.SEEDS]
     for g, (p, q) in enumerate(zip(passes, alone)):
         assert p.kind == q.kind and p.faults == q.faults, g
         assert np.array_equal(p.kept, q.kept) and np.array_equal(p.applied, q.applied), g
@@ -46,7 +46,7 @@ def test_shrink_many_gives_each_seed_the_passes_of_shrinking_it_alone():
 
 def test_a_finished_seed_is_given_no_further_candidates():
     _, _, rounds, _ = _joint()
-    alone = [vg.oracle_passes(k) for k in vg.SEEDS]
+    alone = [vu.oracle_passes(vu.NAME, vu.KINDS, k) for k in vu.SEEDS]
     for g, q in enumerate(alone):
         assert [g in r for r in rounds] == [i < q.rounds for i in range(len(rounds))], g
     one_round = [g for g, q in enumerate(alone) if q.rounds == 1]
@@ -55,8 +55,8 @@ def test_a_finished_seed_is_given_no_further_candidates():
 
 def test_each_result_is_one_minimal_at_its_own_seed():
     passes = _joint()[0]
-    for k, p in zip(vg.SEEDS, passes):
-        vg.assert_one_minimal(k, p)
+    for k, p in zip(vu.SEEDS, passes):
+        vu.assert_one_minimal(vu.NAME, p, k)
         assert p.kept.size < p.faults or p.faults == 0
 
 

@@ -75,12 +75,11 @@ def gpu_many():
 
 
 def _shrink_alone(k):
-    from tests import variant_groups_util as vg
-    base, code, _ = vg.recorded(k)
+    base, code, _ = vu.recorded(NAME, k)
     idx, edits, _ = shrink.edit_list(base, KINDS)
 
     def ev(applied):  # (no memo: every candidate is replayed, as a user's run would)
-        return np.array([vg.replay(k, shrink.apply_edits(base, idx, edits, a))[0] for a in applied])
+        return np.array([vu.replay(NAME, shrink.apply_edits(base, idx, edits, a), k)[0] for a in applied])
     p = shrink.shrink_passes(ev, base, KINDS, code)
     return p.faults, int(p.kept.size), p.rounds, p.candidates
 
