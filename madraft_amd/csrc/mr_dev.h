@@ -187,19 +187,16 @@ struct Dev {
   uint32_t C, n, log_cap, apply_cap, M, K, hb, elo, ehi, max_events;
   uint32_t null_raft, unrel_flag, trace_clusters, trace_cap, scenario, iters, safety, bugs, links;
   uint64_t seed0;  // seed of cluster 0 = seed_base + cluster_base
-  uint32_t* cs32;
-  uint64_t* cs64;
-  uint32_t* nd32;   // [C][n][NREC]
-  uint32_t* tmr;    // [n][C] node timers (registers during a launch)
-  uint32_t* ms32;   // [C][M][MREC]
-  uint64_t* mkey;   // [M][C]
-  LE* log;  // [C][n][log_cap] ring per node
-  LE* pay;  // [C][M][K] AppendEntries payload per message slot
-  SE* stor;         // [C][apply_cap]   tester storage (tester.rs:366-428)
-  uint32_t* kt32;   // [C][nthr][KT_STRIDE] (spawning scenarios)
-  uint32_t* kv32;   // [C][n][KVREC]        (kvraft only)
-  uint32_t* kvs32;  // [C][n][KVS_W]        persisted KV snapshots (maxraftstate)
-  uint32_t* kring;  // [C][KV_RING][KRW]    recent KV snapshots by index (maxraftstate)
+  // the batch's arrays, these and those below without a shape: the rows of MR_DEV_ARRAYS
+  uint32_t* cs32; uint64_t* cs64; uint32_t* nd32;
+  uint32_t* tmr;    // node timers (registers during a launch)
+  uint32_t* ms32; uint64_t* mkey;
+  LE* log;          // ring per node
+  LE* pay;          // AppendEntries payload per message slot
+  SE* stor;         // tester storage (tester.rs:366-428)
+  uint32_t* kt32; uint32_t* kv32;
+  uint32_t* kvs32;  // persisted KV snapshots (maxraftstate)
+  uint32_t* kring;  // recent KV snapshots by index (maxraftstate)
   uint4* dtab;      // keyed decisions {stream << 16 | entity, seq, w0, w1}, else null:
                     // replay: CSR rows, cluster c's sorted by key at [doff[c], doff[c + 1]);
                     // record: [C][dcap], appended in draw order
@@ -216,19 +213,19 @@ struct Dev {
   uint2* vwords;    // [edits] an edit's replacement words (w0, w1), the groups' one after the other
   uint32_t* vmask;  // [C][vW] bit j of cluster c's row: c takes its group's edit j
   uint32_t vW;      // mask words per cluster = ceil(the widest group's edits / 32)
-  uint64_t* cval;   // [C][3][CHURN_VCAP]   churn clients' committed values (churn only)
-  uint32_t* cidx;   // [C][3][CHURN_VCAP]   ... and the index each was seen at
-  uint32_t* cfg32;  // [C][n][CFG_CAP][CFGW] shard_ctrler config stores
-  uint32_t* op32;   // [C][OP_CAP][OPW]       shard_ctrler operations
+  uint64_t* cval;   // churn clients' committed values
+  uint32_t* cidx;   // ... and the index each was seen at
+  uint32_t* cfg32;  // shard_ctrler config stores
+  uint32_t* op32;   // shard_ctrler operations
   uint32_t nthr;    // thread slots of kt32 (0 = none)
-  mr_event* trace;  // [trace_clusters][trace_cap]
-  uint64_t* tdig;   // [trace_clusters][trace_cap] apply digest of each record (ABI 4)
-  uint64_t* tapp;   // [trace_clusters][trace_cap][2] KV command, key hash after it (ABI 4)
-  uint64_t* adig;   // [trace_clusters][MR_MAX_NODES][2] per node: digest sum, invalid flag
-  uint32_t* led;    // [C][LED_W] MR_F_SAFETY: bit t = a leader was elected in term t
-  uint32_t* lin32;  // [C][KV_KEYS][KV_APP][LINW] kvraft linearizability bookkeeping (§9a, §9b)
+  mr_event* trace;
+  uint64_t* tdig;   // apply digest of each record (ABI 4)
+  uint64_t* tapp;   // KV command, key hash after it (ABI 4)
+  uint64_t* adig;   // per node: digest sum, invalid flag
+  uint32_t* led;    // MR_F_SAFETY: bit t = a leader was elected in term t
+  uint32_t* lin32;  // kvraft linearizability bookkeeping (§9a, §9b)
   uint32_t lin15;   // generic_test_linearizability layout (§9b): key records / bookkeeping
-  uint32_t* remaining;  // [2]: clusters without verdict after a step launch; next unclaimed cluster
+  uint32_t* remaining;  // clusters without verdict after a step launch; next unclaimed cluster
   uint32_t L;           // clusters per launch: lane l starts with cluster c0 + l (chunk [c0, c0 + L))
   uint32_t lpw;         // lanes of each 64-lane block that hold a cluster (64, 32, 16; the rest idle)
   uint32_t c0;          // first cluster of this launch's chunk
@@ -237,13 +234,13 @@ struct Dev {
   uint32_t nheld;       // ... the clusters the previous launch's lanes still held
   uint32_t* held_in;    // [L] those clusters (streaming)
   uint32_t* held_out;   // [L] this launch's (index = its remaining[0] count)
-  unsigned long long* prof;  // [PROF_SLOTS] wave-cycle profile (MR_PROF builds only)
-  uint4* tfr;       // [C][TF_Q] the tester coroutine frame, one cluster-major 80-B record
-  uint32_t* kwk;    // [C][kws(nthr)][2] thread slots' {tid, wake}: the scheduler's keys, packed
+  unsigned long long* prof;  // wave-cycle profile (MR_PROF builds only)
+  uint4* tfr;       // the tester coroutine frame, one cluster-major 80-B record
+  uint32_t* kwk;    // thread slots' {tid, wake}: the scheduler's keys, packed
   uint32_t pool;    // the batch runs on pool_kernel (has_pool): 32-bit keys with the AE bit
-  uint32_t* guard;  // [4] MR_GUARD builds: an out-of-range index {tag, cluster, index, bound}
+  uint32_t* guard;  // MR_GUARD builds: an out-of-range index {tag, cluster, index, bound}
   uint32_t gprobe;  // MR_GUARD builds, MR_GUARD_PROBE set: cluster 0's first delivery reads slot M
-  unsigned long long* pcnt;  // [CNT__N] pool_kernel: the workgroups' counter sums (64-bit; reduce adds them)
+  unsigned long long* pcnt;  // pool_kernel: the workgroups' counter sums (64-bit; reduce adds them)
   uint32_t krows;   // the 7-server Raft pool: message slots whose keys live in LDS (the rest in HBM)
 };
 // words-pairs per cluster of kwk: the thread slots rounded up to whole 16-B quads (two slots each;
@@ -257,28 +254,17 @@ constexpr uint32_t PROF_SLOTS = 96;  // 64..94: pool_kernel statistics (MR_PROF,
 // later term is a simulator limit (MR_FAIL_SIM_CAPACITY); figure_8 peaks at term 177
 constexpr uint32_t LED_W = 64, LED_TERMS = 32 * LED_W;
 
-// The kind column of madraft_sim.h's MR_SCENARIO_TABLE. Device code calls nthr() (below) with the
-// template constant S but not in constant-evaluated contexts (`D.nthr = nthr(S)`), so an
-// out-of-line copy of it, and of these compares, is emitted into the code objects: they keep
-// their compare form, and every row is checked against them here.
-constexpr bool is_kv(uint32_t s) {
-  return (s >= MR_SCN_KV_BASIC_3A && s <= MR_SCN_KV_UNRELIABLE_3A) ||
-         (s >= MR_SCN_KV_MANY_PARTITIONS_ONE_CLIENT_3A &&
-          s <= MR_SCN_KV_SNAPSHOT_UNRELIABLE_RECOVER_CONCURRENT_PARTITION_LINEARIZABLE_3B);
-}
-constexpr bool is_ctrl(uint32_t s) { return s == MR_SCN_CTRL_BASIC_4A || s == MR_SCN_CTRL_MULTI_4A; }
+// The kind column of madraft_sim.h's MR_SCENARIO_TABLE (0 for an id without a row: no service)
+constexpr bool is_kv(uint32_t s) { return mr_scn_is_kv(s); }
+constexpr bool is_ctrl(uint32_t s) { return mr_scn_kind(s) == MR_KIND_CTRL; }
 // scenarios served by the clerk / server request path (kvraft + shard_ctrler)
 constexpr bool is_svc(uint32_t s) { return is_kv(s) || is_ctrl(s); }
-#define MR_ROW_(id, sym, name, n, kind, slots, exact, pool)                                \
-  static_assert(is_kv(id) == (MR_KIND_##kind == MR_KIND_KV) &&                             \
-                    is_ctrl(id) == (MR_KIND_##kind == MR_KIND_CTRL) && id < MR_SCN_COUNT_, \
-                name ": is_kv / is_ctrl disagree with the kind column, or rows out of id order");
+#define MR_ROW_(id, sym, name, n, kind, slots, exact, pool) static_assert(id < MR_SCN_COUNT_, name);
 MR_SCENARIO_TABLE(MR_ROW_)
 #undef MR_ROW_
-static_assert(!is_svc(MR_SCN_NONE) && !is_svc(MR_SCN_COUNT_), "ids without a row are no service");
 // generic_test(nclients, unreliable, crash, partitions, maxraftstate) of a kvraft scenario
 // (kvraft/tests.rs:222-384, 494-522); snapshot_rpc / snapshot_size use maxraftstate too
-struct KvGen { uint32_t nc; bool unrel, crash, part; uint32_t maxraft; bool lin; };
+struct KvGen { uint32_t nc; bool unrel, crash, part; uint32_t maxraft; };
 constexpr KvGen kv_gen(uint32_t s) {
   switch (s) {
     case MR_SCN_KV_BASIC_3A: return {1, false, false, false};
@@ -300,11 +286,11 @@ constexpr KvGen kv_gen(uint32_t s) {
     case MR_SCN_KV_SNAPSHOT_UNRELIABLE_3B: return {5, true, false, false, 1000};
     case MR_SCN_KV_SNAPSHOT_UNRELIABLE_RECOVER_3B: return {5, true, true, false, 1000};
     case MR_SCN_KV_SNAPSHOT_UNRELIABLE_RECOVER_CONCURRENT_PARTITION_3B: return {5, true, true, true, 1000};
-    // generic_test_linearizability (15 clients, 7 servers; SEMANTICS §9b)
-    case MR_SCN_KV_PERSIST_PARTITION_UNRELIABLE_LINEARIZABLE_3A: return {15, true, true, true, 0, true};
+    // generic_test_linearizability (15 clients, 7 servers; SEMANTICS §9b): mr_scn_is_lin15
+    case MR_SCN_KV_PERSIST_PARTITION_UNRELIABLE_LINEARIZABLE_3A: return {15, true, true, true, 0};
     case MR_SCN_KV_SNAPSHOT_UNRELIABLE_RECOVER_CONCURRENT_PARTITION_LINEARIZABLE_3B:
-      return {15, true, true, true, 1000, true};
-    default: return {0, false, false, false, 0, false};
+      return {15, true, true, true, 1000};
+    default: return {0, false, false, false, 0};
   }
 }
 // the service pool's applier continuation (mr_kernel.hip AP_CAP) is built for the 15-client
@@ -314,20 +300,17 @@ constexpr KvGen kv_gen(uint32_t s) {
 // backlogs: the extra kind and the registers cost more than the balance gains)
 // (the snapshotting linearizable 3B body with it, cap 5: 89.8 K -> 88.5 K seeds/s, -1.4 %,
 // profiles/r06_ab_kv47.txt)
-constexpr bool ap_cont(uint32_t s) { return kv_gen(s).lin && kv_gen(s).maxraft == 0; }
+constexpr bool ap_cont(uint32_t s) { return mr_scn_is_lin15(s) && kv_gen(s).maxraft == 0; }
 // the KV snapshot copy's chunk (quads whose loads issue together, kv_snapshot): 8 for
 // the 15-client linearizable body, 4 for the others. Same box (profiles/r06_ab_kc.txt): the
 // snapshotting linearizable 3B body 89.7 K -> 93.6 K seeds/s with 8 (+4.4 %; 16: -5 %), the 5-client
 // 3B body 238 K -> 220 K (-7.5 %: its kernel spills the larger chunk)
-constexpr uint32_t kv_chunk(uint32_t s) { return kv_gen(s).lin ? 8u : 4u; }
-constexpr bool is_churn(uint32_t s) {
-  return s == MR_SCN_RELIABLE_CHURN_2C || s == MR_SCN_UNRELIABLE_CHURN_2C;
-}
+constexpr uint32_t kv_chunk(uint32_t s) { return mr_scn_is_lin15(s) ? 8u : 4u; }
 // tester thread slots (slot 0 = the test body): kvraft 1 + 5 clients, churn 1 + 3
 // clients, unreliable_agree_2c up to 63 concurrent one() tasks
 constexpr uint32_t nthr(uint32_t s) {
   return is_kv(s) ? (kv_gen(s).nc + 2u > 6u ? kv_gen(s).nc + 2u : 6u)  // + test body, partitioner
-         : is_ctrl(s) ? 11u : is_churn(s) ? 4u
+         : is_ctrl(s) ? 11u : mr_scn_is_churn(s) ? 4u
          : s == MR_SCN_UNRELIABLE_AGREE_2C ? 64u : 0u;
 }
 
@@ -379,18 +362,12 @@ constexpr uint32_t pool_max_slots(uint32_t s, uint32_t n) { return is_svc(s) || 
                 name ": the default server count below 8 has its exact instance");
 MR_SCENARIO_TABLE(MR_ROW_)
 #undef MR_ROW_
-// scenarios whose test body starts the tester with service snapshots (t_new(snapshot = true),
-// tester.rs:303-325 SNAPSHOT_INTERVAL): snap_common's five 2D tests. node_apply_coop specializes
-// on it at compile time and checks it against the runtime mode (x.netmode bit 1).
-constexpr bool uses_service_snapshots(uint32_t s) {
-  return s >= MR_SCN_SNAPSHOT_BASIC_2D && s <= MR_SCN_SNAPSHOT_INSTALL_UNRELIABLE_CRASH_2D;
-}
-// scenarios in which a log can be compacted: the service snapshots of snap_common or a kvraft
+// scenarios in which a log can be compacted: the service snapshots of snap_common (mr_scn_is_snap2d:
+// t_new(snapshot = true), tester.rs:303-325 SNAPSHOT_INTERVAL; node_apply_coop specializes on it
+// at compile time and checks it against the runtime mode, x.netmode bit 1) or a kvraft
 // maxraftstate. Everywhere else snap stays 0, so no InstallSnapshot is ever sent (the node
 // event compiles that path out of its send loop)
-constexpr bool has_snaps(uint32_t s) {
-  return uses_service_snapshots(s) || kv_gen(s).maxraft > 0;
-}
+constexpr bool has_snaps(uint32_t s) { return mr_scn_is_snap2d(s) || kv_gen(s).maxraft > 0; }
 // test bodies that crash and restart servers (crash1 / start1, tester.rs:293-333): persist1-3,
 // figure_8 and its unreliable crash variant, the 2D crash variants, the churn tests
 constexpr bool restarts_servers(uint32_t s) {
@@ -398,6 +375,94 @@ constexpr bool restarts_servers(uint32_t s) {
          s == MR_SCN_UNRELIABLE_CHURN_2C || s == MR_SCN_SNAPSHOT_INSTALL_CRASH_2D ||
          s == MR_SCN_SNAPSHOT_INSTALL_UNRELIABLE_CRASH_2D || s == MR_SCN_FIGURE_8_UNRELIABLE_CRASH;
 }
+// ---- the batch's device arrays, one row each, in the order they are carved from the batch's one
+// allocation (every array 256-B aligned): X(Dev member, elements, present, reset)
+//   elements  over the config: C clusters, n servers, M message slots, K = ae_max, log_cap, apply_cap,
+//             trace_clusters (0 unless MR_F_TRACE), trace_cap, safety (1 with MR_F_SAFETY, else 0), and
+//             the scenario s (nthr(s) thread slots, kws() of them for the scheduler keys)
+//   present   over s; an absent or empty array is a null pointer
+//   reset     ZERO(k): the k-th memset of mr_batch_reset; KERNEL: reset_kernel initialises it; NONE: a
+//             run writes it before it reads it (the row says why); GUARD: ZERO in MR_GUARD builds
+#define MR_DEV_ARRAYS(X)                                                                          \
+  X(cs32, CS_STRIDE * C, true, KERNEL)                                                            \
+  X(cs64, C64_STRIDE * C, true, KERNEL)                                                           \
+  X(nd32, NREC * n * C, true, KERNEL)                                                             \
+  X(tmr, n * C, true, KERNEL)                                                                     \
+  X(ms32, MREC * M * C, true, NONE) /* a slot's record is written when its key is: at the send */ \
+  X(mkey, M * C, true, KERNEL)                                                                    \
+  X(log, C * n * log_cap, true, NONE) /* entries up to NF_LAST, each written by its append */     \
+  X(pay, C * M * K, true, NONE)       /* written when the slot's message takes a payload */       \
+  X(stor, C * apply_cap, true, ZERO(2))                                                           \
+  X(kt32, KT_STRIDE * nthr(s) * C, nthr(s) > 0, KERNEL)                                           \
+  X(kwk, 2 * kws(nthr(s)) * C, nthr(s) > 0, KERNEL)                                               \
+  X(kv32, KVREC * n * C, is_svc(s), ZERO(7))                                                      \
+  X(lin32, KV_KEYS * KV_APP * LINW * C, is_kv(s), ZERO(8))                                        \
+  X(kvs32, KVS_W * n * C, kv_gen(s).maxraft > 0, ZERO(9))                                         \
+  X(kring, KRW * KV_RING * C, kv_gen(s).maxraft > 0, ZERO(10))                                    \
+  X(cfg32, CFG_CAP * CFGW * n * C, is_ctrl(s), KERNEL)                                            \
+  X(op32, OP_CAP * OPW * C, is_ctrl(s), NONE) /* rows below CS_NOPS, each written by its clerk */ \
+  X(cval, 3 * CHURN_VCAP * C, mr_scn_is_churn(s), NONE) /* up to the client's own count */        \
+  X(cidx, 3 * CHURN_VCAP * C, mr_scn_is_churn(s), NONE) /* as cval */                             \
+  X(led, safety * LED_W * C, true, ZERO(3))                                                            \
+  X(trace, trace_clusters * trace_cap, true, NONE) /* records below CS_TRACEN */                  \
+  X(tdig, trace_clusters * trace_cap, true, ZERO(4))                                              \
+  X(tapp, trace_clusters * trace_cap * 2, true, ZERO(5))                                          \
+  X(adig, trace_clusters * MR_MAX_NODES * 2, true, ZERO(6))                                       \
+  X(remaining, 2, true, NONE)  /* copied from the host before every launch */                     \
+  X(prof, PROF_SLOTS, true, NONE) /* zeroed at create: a profile sums over the batch's runs */    \
+  X(guard, 4, true, GUARD)        /* zeroed at create */                                          \
+  X(pcnt, CNT__N, true, ZERO(0))                                                                  \
+  X(tfr, TF_Q * C, true, KERNEL)
+#define MR_ROW_(m, elements, present, reset) A_##m,
+enum DevArray : uint32_t { MR_DEV_ARRAYS(MR_ROW_) A__N };
+#undef MR_ROW_
+constexpr int RST_NONE = -2, RST_KERNEL = -1;  // (a ZERO row: its place k)
+#define RST_ZERO(k) (k)
+#if MR_GUARD
+#define RST_GUARD RST_ZERO(1)  // a violation belongs to the run it happened in
+#else
+#define RST_GUARD RST_NONE
+#endif
+#define MR_ROW_(m, elements, present, reset) RST_##reset,
+constexpr int k_dev_reset[A__N] = {MR_DEV_ARRAYS(MR_ROW_)};  // by DevArray
+#undef MR_ROW_
+// a batch of scenario s has array a: the kernels' template constant S folds it, so an array's
+// presence is typed out in its row only
+constexpr bool dev_has(uint32_t s, DevArray a) {
+#define MR_ROW_(m, elements, present, reset) if (a == A_##m) return present;
+  MR_DEV_ARRAYS(MR_ROW_)
+#undef MR_ROW_
+  return false;
+}
+// Dev's fields the scenario alone fixes: set by the host at create, and by fix_scenario<S>, where they fold
+constexpr void scenario_fixed(Dev& D, uint32_t s) {
+  D.nthr = nthr(s);
+  D.links = kv_gen(s).part ? 1u : 0u;      // server-link cuts (CS_CUT) can exist
+  D.lin15 = mr_scn_is_lin15(s) ? 1u : 0u;  // generic_test_linearizability layout (SEMANTICS §9b)
+}
+// Where a batch of config c keeps its arrays: a function of the config alone, so it is checked
+// without a device (tests/test_abi.py). bytes 0: absent or empty; off[A__N]: the allocation's size
+struct DevLayout { size_t bytes[A__N], off[A__N + 1]; };
+inline DevLayout dev_layout(const mr_cfg& c) {
+  const uint64_t C = c.n_clusters, n = c.n_nodes, M = c.msg_slots, K = c.ae_max, log_cap = c.log_cap,
+                 apply_cap = c.apply_cap, trace_cap = c.trace_cap, trace_clusters = (c.flags & MR_F_TRACE) ? c.trace_clusters : 0u;
+  const uint32_t s = c.scenario, safety = (c.flags & MR_F_SAFETY) ? 1u : 0u;
+  DevLayout L{};
+#define MR_ROW_(m, elements, present, reset) \
+  L.bytes[A_##m] = dev_has(s, A_##m) ? (elements) * sizeof(*Dev().m) : 0u;
+  MR_DEV_ARRAYS(MR_ROW_)
+#undef MR_ROW_
+  for (uint32_t a = 0; a < A__N; a++) L.off[a + 1] = L.off[a] + ((L.bytes[a] + 255) & ~size_t(255));
+  return L;
+}
+// D's array members point into the allocation at `base` as L lays it out
+inline void dev_carve(Dev& D, const DevLayout& L, char* base) {
+#define MR_ROW_(m, elements, present, reset) \
+  D.m = L.bytes[A_##m] ? reinterpret_cast<decltype(D.m)>(base + L.off[A_##m]) : nullptr;
+  MR_DEV_ARRAYS(MR_ROW_)
+#undef MR_ROW_
+}
+
 #define MR_INST_ROW_(id, sym, name, n, kind, slots, exact, pool) MR_INST(id)
 #define MR_ALL_SCNS MR_SCENARIO_TABLE(MR_INST_ROW_)  // MR_INST(id) for every row of the table
 

@@ -145,7 +145,7 @@ struct mr_batch {
   mr_cfg cfg;
   Dev D;
   void* base = nullptr;
-  size_t bytes = 0;
+  DevLayout lay;  // where `base` holds D's arrays, and what a reset zeroes
   unsigned long long* red = nullptr;
   uint32_t* h_remaining = nullptr;  // [2]: remaining, next unclaimed cluster (D.remaining)
   uint32_t* h_ctl0 = nullptr;       // [2]: {0, L}, copied to D.remaining before each launch
@@ -258,20 +258,19 @@ static int mr_batch_create_impl(const mr_cfg* cfg, mr_batch** out) {
   b->cfg = *cfg;
   Dev& D = b->D;
   std::memset(&D, 0, sizeof D);
-  const uint64_t C = cfg->n_clusters, n = cfg->n_nodes, M = cfg->msg_slots, K = cfg->ae_max;
+  const uint64_t C = cfg->n_clusters, n = cfg->n_nodes, M = cfg->msg_slots;
   D.C = (uint32_t)C;
   D.L = cfg->lanes && cfg->lanes < C ? cfg->lanes : (uint32_t)C;  // no tape: capacity (below)
   D.stream = (cfg->flags & MR_F_STREAM) ? 1u : 0u;
   D.n = (uint32_t)n; D.log_cap = cfg->log_cap; D.apply_cap = cfg->apply_cap;
-  D.M = (uint32_t)M; D.K = (uint32_t)K; D.hb = cfg->hb_us; D.elo = cfg->elect_lo_us;
+  D.M = (uint32_t)M; D.K = cfg->ae_max; D.hb = cfg->hb_us; D.elo = cfg->elect_lo_us;
   D.ehi = cfg->elect_hi_us; D.max_events = cfg->max_events;
   D.null_raft = (cfg->flags & MR_F_NULL_RAFT) ? 1u : 0u;
   D.unrel_flag = (cfg->flags & MR_F_UNRELIABLE) ? 1u : 0u;
   D.safety = (cfg->flags & MR_F_SAFETY) ? 1u : 0u;
   D.bugs = cfg->flags & (MR_F_BUG_VOTE_TWICE | MR_F_BUG_VOTE_STALE | MR_F_BUG_NO_PREV_CHECK |
                          MR_F_BUG_NO_DEDUP | MR_F_BUG_STALE_READ | MR_F_BUG_NO_APPLY_CHECK);
-  D.links = kv_gen(cfg->scenario).part ? 1u : 0u;  // server-link cuts (CS_CUT) can exist
-  D.lin15 = mr_scn_is_lin15(scn) ? 1u : 0u;  // generic_test_linearizability layout (SEMANTICS §9b)
+  scenario_fixed(D, scn);
   D.trace_clusters = (cfg->flags & MR_F_TRACE) ? cfg->trace_clusters : 0u;
   D.trace_cap = cfg->trace_cap;
   D.scenario = scn;
@@ -281,60 +280,15 @@ static int mr_batch_create_impl(const mr_cfg* cfg, mr_batch** out) {
   D.seed0 = cfg->seed_base + cfg->cluster_base;
   D.pool = !(cfg->flags & MR_F_RECORD) && use_pool(scn, (uint32_t)n, (uint32_t)M) ? 1u : 0u;
 
-  // carve one allocation; every array 256-B aligned
-  struct Item { void** p; size_t bytes; };
-  std::vector<Item> items;
-  auto add = [&](auto** p, size_t count) {
-    items.push_back({reinterpret_cast<void**>(p), count * sizeof(**p)});
-  };
   // field matrices use 32-bit element offsets in the kernels
   const uint64_t lim = 1ull << 32;
   if ((uint64_t)CS_STRIDE * C >= lim || (uint64_t)C64_STRIDE * C >= lim || M * C >= lim) {
     delete b;
     return set_err("n_clusters too large for one batch (32-bit field offsets)");
   }
-  add(&D.cs32, (size_t)CS_STRIDE * C);
-  add(&D.cs64, (size_t)C64_STRIDE * C);
-  add(&D.nd32, (size_t)NREC * n * C);
-  add(&D.tmr, n * C);
-  add(&D.ms32, (size_t)MREC * M * C);
-  add(&D.mkey, (size_t)M * C);
-  add(&D.log, C * n * cfg->log_cap);
-  add(&D.pay, C * M * K);
-  add(&D.stor, C * cfg->apply_cap);
-  // scenario-only arrays: spawned tester threads, kvraft servers, churn values
-  D.nthr = nthr(scn);
-  if (D.nthr) add(&D.kt32, (size_t)KT_STRIDE * D.nthr * C);
-  if (D.nthr) add(&D.kwk, (size_t)2 * kws(D.nthr) * C);
-  if (is_svc(scn)) add(&D.kv32, (size_t)KVREC * n * C);
-  if (is_kv(scn)) add(&D.lin32, (size_t)KV_KEYS * KV_APP * LINW * C);
-  if (kv_gen(scn).maxraft) {
-    add(&D.kvs32, (size_t)KVS_W * n * C);
-    add(&D.kring, (size_t)KRW * KV_RING * C);
-  }
-  if (is_ctrl(scn)) {
-    add(&D.cfg32, (size_t)CFG_CAP * CFGW * n * C);
-    add(&D.op32, (size_t)OP_CAP * OPW * C);
-  }
-  if (is_churn(scn)) {
-    add(&D.cval, (size_t)3 * CHURN_VCAP * C);
-    add(&D.cidx, (size_t)3 * CHURN_VCAP * C);
-  }
-  if (D.safety) add(&D.led, (size_t)LED_W * C);
-  add(&D.trace, (size_t)D.trace_clusters * D.trace_cap);
-  add(&D.tdig, (size_t)D.trace_clusters * D.trace_cap);       // apply digests (ABI 4)
-  add(&D.tapp, (size_t)D.trace_clusters * D.trace_cap * 2u);  // KV applies (ABI 4)
-  add(&D.adig, (size_t)D.trace_clusters * MR_MAX_NODES * 2u);
-  add(&D.remaining, 2);
-  add(&D.prof, PROF_SLOTS);
-  add(&D.guard, 4);
-  add(&D.pcnt, CNT__N);
-  add(&D.tfr, (size_t)TF_Q * C);
-  size_t total = 0;
-  for (auto& it : items) total += (it.bytes + 255) & ~size_t(255);
-
+  b->lay = dev_layout(*cfg);  // one allocation; every array 256-B aligned (mr_dev.h MR_DEV_ARRAYS)
   hipError_t e = hipSetDevice(cfg->device);
-  if (e == hipSuccess) e = hipMalloc(&b->base, total);
+  if (e == hipSuccess) e = hipMalloc(&b->base, b->lay.off[A__N]);
   if (e == hipSuccess) e = hipMalloc(&b->red, RED_N * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipHostMalloc(&b->h_remaining, 2 * sizeof(uint32_t));
   if (e == hipSuccess) e = hipHostMalloc(&b->h_ctl0, 2 * sizeof(uint32_t));
@@ -342,17 +296,12 @@ static int mr_batch_create_impl(const mr_cfg* cfg, mr_batch** out) {
   if (e == hipSuccess) e = hipEventCreate(&b->ev0);
   if (e == hipSuccess) e = hipEventCreate(&b->ev1);
   if (e != hipSuccess) {
-    std::string msg = std::string("allocation of ") + std::to_string(total) + " B failed: " +
+    std::string msg = std::string("allocation of ") + std::to_string(b->lay.off[A__N]) + " B failed: " +
                       hipGetErrorString(e);
     mr_batch_destroy(b);
     return set_err(msg);
   }
-  b->bytes = total;
-  char* p = static_cast<char*>(b->base);
-  for (auto& it : items) {
-    *it.p = it.bytes ? p : nullptr;
-    p += (it.bytes + 255) & ~size_t(255);
-  }
+  dev_carve(D, b->lay, static_cast<char*>(b->base));
   if (cfg->flags & MR_F_RECORD) {
     Tables t;  // (the tape is written before it is read: not filled)
     e = hipMalloc(&t.tape, (size_t)C * cfg->tape_cap * sizeof(uint4));
@@ -416,28 +365,13 @@ static int enqueue_reset(mr_batch* b, uint64_t seed_base) {
   b->resume = false;
   b->D.seed0 = seed_base + b->cfg.cluster_base;
   HIPCHK(hipSetDevice(b->cfg.device));
-  HIPCHK(hipMemsetAsync(b->D.pcnt, 0, CNT__N * sizeof(unsigned long long), b->stream));
-#if MR_GUARD  // a violation belongs to the run it happened in
-  HIPCHK(hipMemsetAsync(b->D.guard, 0, 4 * sizeof(uint32_t), b->stream));
+  for (int k = 0; k < (int)A__N; k++)  // the table's ZERO rows this batch has, by their place k
+    for (uint32_t a = 0; a < A__N; a++)
+      if (k_dev_reset[a] == k && b->lay.bytes[a])
+        HIPCHK(hipMemsetAsync(static_cast<char*>(b->base) + b->lay.off[a], 0, b->lay.bytes[a], b->stream));
+#if MR_GUARD
   b->D.gprobe = std::getenv("MR_GUARD_PROBE") ? 1u : 0u;
 #endif
-  HIPCHK(hipMemsetAsync(b->D.stor, 0, (size_t)b->D.C * b->D.apply_cap * sizeof(SE), b->stream));
-  if (b->D.led)
-    HIPCHK(hipMemsetAsync(b->D.led, 0, (size_t)b->D.C * LED_W * sizeof(uint32_t), b->stream));
-  if (b->D.trace_clusters) {  // apply digests: every node starts at 0 (valid), no record yet
-    HIPCHK(hipMemsetAsync(b->D.tdig, 0, (size_t)b->D.trace_clusters * b->D.trace_cap * 8u, b->stream));
-    HIPCHK(hipMemsetAsync(b->D.tapp, 0, (size_t)b->D.trace_clusters * b->D.trace_cap * 16u, b->stream));
-    HIPCHK(hipMemsetAsync(b->D.adig, 0, (size_t)b->D.trace_clusters * MR_MAX_NODES * 16u, b->stream));
-  }
-  if (b->D.kv32)
-    HIPCHK(hipMemsetAsync(b->D.kv32, 0, (size_t)b->D.C * b->D.n * KVREC * sizeof(uint32_t), b->stream));
-  if (b->D.lin32)
-    HIPCHK(hipMemsetAsync(b->D.lin32, 0, (size_t)b->D.C * KV_KEYS * KV_APP * LINW * sizeof(uint32_t),
-                          b->stream));
-  if (b->D.kvs32) {
-    HIPCHK(hipMemsetAsync(b->D.kvs32, 0, (size_t)b->D.C * b->D.n * KVS_W * sizeof(uint32_t), b->stream));
-    HIPCHK(hipMemsetAsync(b->D.kring, 0, (size_t)b->D.C * KV_RING * KRW * sizeof(uint32_t), b->stream));
-  }
   HIPCHK(launch_reset(b->D, b->stream));
   return 0;
 }

@@ -835,15 +835,15 @@ template <uint32_t S>
 DI Dev dev_launder(const Dev& D0) {
   Dev D = D0;
   D.log = glp(D0.log); D.stor = glp(D0.stor); D.cs32 = glp(D0.cs32); D.nd32 = glp(D0.nd32);
-  if (is_svc(S)) D.kv32 = glp(D0.kv32);
-  if (kv_gen(S).maxraft > 0) { D.kvs32 = glp(D0.kvs32); D.kring = glp(D0.kring); }
+  if (dev_has(S, A_kv32)) D.kv32 = glp(D0.kv32);
+  if (dev_has(S, A_kvs32)) { D.kvs32 = glp(D0.kvs32); D.kring = glp(D0.kring); }
   D.trace = glp(D0.trace);
   D.apply_cap = glu(D0.apply_cap); D.log_cap = glu(D0.log_cap); D.bugs = glu(D0.bugs);
   D.trace_clusters = glu(D0.trace_clusters); D.trace_cap = glu(D0.trace_cap);
   D.ms32 = glp(D0.ms32); D.pay = glp(D0.pay); D.tmr = glp(D0.tmr);
   if (D0.led) D.led = glp(D0.led);
-  if (is_kv(S)) D.lin32 = glp(D0.lin32);
-  if (nthr(S) > 0) { D.kt32 = glp(D0.kt32); D.kwk = glp(D0.kwk); }
+  if (dev_has(S, A_lin32)) D.lin32 = glp(D0.lin32);
+  if (dev_has(S, A_kt32)) { D.kt32 = glp(D0.kt32); D.kwk = glp(D0.kwk); }
   D.seed0 = ((uint64_t)glu((uint32_t)(D0.seed0 >> 32)) << 32) | glu((uint32_t)D0.seed0);
   D.M = glu(D0.M); D.K = glu(D0.K); D.hb = glu(D0.hb); D.elo = glu(D0.elo); D.ehi = glu(D0.ehi);
   D.safety = glu(D0.safety); D.max_events = glu(D0.max_events);
@@ -956,11 +956,11 @@ DI void node_apply(const Dev& D, X& x, uint32_t me, NC& d, uint32_t& kvready, ui
 // that are not in this call never contribute a value.
 template <uint32_t S>
 DI void node_apply_coop(const Dev& D, X& x, uint32_t me, NC& d) {
-  // snap_common (the 2D tests, uses_service_snapshots) runs with service snapshots:
+  // snap_common (the 2D tests, mr_scn_is_snap2d) runs with service snapshots:
   // t_new(snapshot = true) precedes every node event of such a batch, so the mode is the same
   // for every lane here. A scenario whose runtime mode (x.netmode bit 1, what node_apply
   // reads) disagrees would skip or invent snapshots: it fails loudly instead.
-  constexpr bool snapmode = uses_service_snapshots(S);
+  constexpr bool snapmode = mr_scn_is_snap2d(S);
   if (((x.netmode >> 1) & 1u) != (snapmode ? 1u : 0u)) { fail(D, x, MR_FAIL_SIM_BAD_PROGRAM); return; }
   const uint32_t cnt = d.commit > d.applied ? d.commit - d.applied : 0u;
   const uint32_t base = d.applied + 1u, len0 = d.slen;
@@ -2226,19 +2226,15 @@ constexpr uint32_t step_waves() {
 }
 // exact-size instances (NB < 8, mr_dev.h has_exact): the node count is NB at compile time
 constexpr bool EXACT_N = MR_NB < MR_MAX_NODES;
-// configuration the scenario and the instance fix (mr_host.cpp sets the same values):
+// configuration the scenario and the instance fix (scenario_fixed: the values the host set):
 // compile-time in the kernels, so no loop-invariant predicate on them is kept in scalar registers
 // across their loops
 template <uint32_t S>
 DI void fix_scenario(Dev& D) {
   if constexpr (EXACT_N) D.n = NB;  // the host launches this instance for D.n == NB only
-  D.nthr = nthr(S);
-  D.links = kv_gen(S).part ? 1u : 0u;
-  D.lin15 = kv_gen(S).lin ? 1u : 0u;
-  if constexpr (!is_svc(S)) D.kv32 = nullptr;
-  if constexpr (kv_gen(S).maxraft == 0) D.kvs32 = nullptr;
-  if constexpr (is_svc(S)) __builtin_assume(D.kv32 != nullptr);
-  if constexpr (kv_gen(S).maxraft > 0) __builtin_assume(D.kvs32 != nullptr);
+  scenario_fixed(D, S);
+  if constexpr (dev_has(S, A_kv32)) __builtin_assume(D.kv32 != nullptr); else D.kv32 = nullptr;
+  if constexpr (dev_has(S, A_kvs32)) __builtin_assume(D.kvs32 != nullptr); else D.kvs32 = nullptr;
 }
 template <uint32_t S, uint32_t NBT>
 __global__ void __launch_bounds__(STEP_BLOCK, step_waves<S>()) step_kernel(Dev Din, uint32_t budget) {
@@ -2318,6 +2314,10 @@ __global__ void __launch_bounds__(STEP_BLOCK, step_waves<S>()) step_kernel(Dev D
 #if MR_COMMON
 // RaftTester state before the test body runs (SEMANTICS §3: tester wakes at t = 0)
 __global__ void __launch_bounds__(256) reset_kernel(Dev D) {
+#define MR_ROW_(m, elements, present, reset) | uint32_t(RST_##reset == RST_KERNEL) << A_##m
+  static_assert((0u MR_DEV_ARRAYS(MR_ROW_)) == (1u << A_cs32 | 1u << A_cs64 | 1u << A_nd32 | 1u << A_tmr | 1u << A_mkey |
+                1u << A_tfr | 1u << A_kt32 | 1u << A_kwk | 1u << A_cfg32), "the table's KERNEL rows are those initialised here");
+#undef MR_ROW_
   X x;
   x.c = blockIdx.x * blockDim.x + threadIdx.x;
   if (x.c >= D.C) return;

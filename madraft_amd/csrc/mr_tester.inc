@@ -824,7 +824,7 @@ DI void scn_kv_generic(const Dev& D, X& x, T& t) {
       CS(CS_KVDONE) = 0u;
       for (uint32_t c = 0; c < nc; c++) {
         kv_spawn(D, x, 1 + c, 1 + nc * it + c, c);
-        if constexpr (g.lin) {  // §9b: a client's token counter continues over iterations
+        if constexpr (mr_scn_is_lin15(S)) {  // §9b: a client's token counter continues over iterations
           KT(KT_KIND, 1 + c) = 4u;
           KT(KT_J, 1 + c) = D.lin32[(size_t)x.c * (KV_KEYS * KV_APP * LINW) + LIN15_J + GI(c, LIN_CLI, G_LINJ)];
         }
@@ -866,7 +866,7 @@ DI void scn_kv_generic(const Dev& D, X& x, T& t) {
       }
       JOIN_TO(1 + cli, 4)
     case 4:
-      if constexpr (g.lin) {  // no predicted values: the checker judged every Get (§9b)
+      if constexpr (mr_scn_is_lin15(S)) {  // no predicted values: the checker judged every Get (§9b)
         D.lin32[(size_t)x.c * (KV_KEYS * KV_APP * LINW) + LIN15_J + GI(cli, LIN_CLI, G_LINJ)] = KT(KT_J, 1 + cli);
         cli++;
         GO(3)
@@ -1441,12 +1441,12 @@ DI void thr_step(const Dev& D, X& x, uint32_t slot) {
     c.kvdone = CS(CS_KVDONE);
     const uint32_t kind = KR(KT_KIND);
     if (kv_gen(S).part && kind == 1u) part_step(D, x, slot, kc);
-    else if (kv_gen(S).lin) lin_client_step(D, x, slot, kc);  // kind 4 (§9b)
+    else if (mr_scn_is_lin15(S)) lin_client_step(D, x, slot, kc);  // kind 4 (§9b)
     else if (kind >= 2u) kv_task_step(D, x, slot, kc);
     else kv_client_step(D, x, slot, kc);
   }
   else if constexpr (is_ctrl(S)) ctl_client_step<S>(D, x, slot);
-  else if constexpr (is_churn(S)) churn_step<S>(D, x, slot);
+  else if constexpr (mr_scn_is_churn(S)) churn_step<S>(D, x, slot);
   else agree_thr_step(D, x, slot);
 }
 

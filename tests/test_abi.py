@@ -2,6 +2,7 @@
 declares; the ctypes mirror matches the C struct layout; host-only entry
 points (no GPU needed) behave."""
 import ctypes as C
+import json
 import os
 import re
 import shutil
@@ -298,3 +299,65 @@ def test_pinned_exact_instances(predicates):
         assert build.has_exact(i, build.DEFAULT_N[i]) == (build.DEFAULT_N[i] < 8)
         assert predicates[i, build.DEFAULT_N[i]][0] == (build.DEFAULT_N[i] < 8)
         assert not build.has_exact(i, 8) and not predicates[i, 8][0]
+
+
+# the batches of tests/golden/dev_layout.json, 64 clusters each: scenario, flags, traced clusters
+LAYOUT_CONFIGS = [
+    ("initial_election_2a", "0", 0), ("reliable_churn_2c", "0", 0), ("unreliable_agree_2c", "0", 0),
+    ("unreliable_3a", "0", 0),
+    ("snapshot_unreliable_recover_concurrent_partition_linearizable_3b",
+     "MR_F_SAFETY | MR_F_TRACE", 2),
+    ("multi_4a", "0", 0)]
+LAYOUT_SRC = """
+#include <cstdio>
+#include "{dev}"
+#define MR_ROW_(m, elements, present, reset) #m,
+static const char* const names[] = {{MR_DEV_ARRAYS(MR_ROW_)}};
+static void one(uint32_t scn, uint32_t flags, uint32_t traced) {{
+  mr_cfg c;
+  mr_cfg_defaults(&c, scn);
+  c.n_clusters = 64; c.flags = flags; c.trace_clusters = traced;
+  const mr::DevLayout L = mr::dev_layout(c);
+  for (uint32_t a = 0; a < mr::A__N; a++)
+    std::printf("%s %lld ", names[a], L.bytes[a] ? (long long)L.off[a] : -1ll);
+  std::printf("total %zu reset", L.off[mr::A__N]);
+  for (int k = 0; k < (int)mr::A__N; k++)  // mr_batch_reset's walk: the ZERO rows by their place
+    for (uint32_t a = 0; a < mr::A__N; a++)
+      if (mr::k_dev_reset[a] == k && L.bytes[a]) std::printf(" %s %zu", names[a], L.bytes[a]);
+  std::printf("\\n");
+}}
+int main() {{
+{calls}
+  return 0;
+}}"""
+
+
+@pytest.mark.parametrize("guard", [False, True], ids=["product", "guard"])
+def test_dev_layout_matches_golden(guard):
+    """mr_dev.h's array table gives every array of a batch the byte offset (-1: a null pointer) it
+    had when mr_batch_create typed the carve out, the same total, and mr_batch_reset the memsets
+    it issued then, byte counts and order (MR_GUARD builds: `guard` too), for six batches of 64
+    clusters. The expected numbers are a replay of that code."""
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "dev_layout.json")))
+    assert list(golden) == [t for t, _, _ in LAYOUT_CONFIGS]
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    inc = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "include")
+    calls = "\n".join(f"  one({_abi.SCENARIO_ID[t]}, {flags}, {traced});"
+                      for t, flags, traced in LAYOUT_CONFIGS)
+    with tempfile.TemporaryDirectory() as d:
+        src, exe = os.path.join(d, "l.cpp"), os.path.join(d, "l")
+        open(src, "w").write(LAYOUT_SRC.format(
+            dev=os.path.join(ROOT, "madraft_amd", "csrc", "mr_dev.h"), calls=calls))
+        subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__",
+                        f"-DMR_GUARD={int(guard)}", "-I", inc, "-o", exe, src], check=True)
+        out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
+    lines = out.splitlines()
+    assert len(lines) == len(LAYOUT_CONFIGS)
+    for (test, _, _), line in zip(LAYOUT_CONFIGS, lines):
+        w = line.split()
+        t, r = w.index("total"), w.index("reset")
+        want = golden[test]
+        assert list(zip(w[:t:2], map(int, w[1:t:2]))) == list(want["offsets"].items()), test
+        assert int(w[t + 1]) == want["total"], test
+        assert [[m, int(b)] for m, b in zip(w[r + 1::2], w[r + 2::2])] == \
+            want["reset_guard" if guard else "reset"], test

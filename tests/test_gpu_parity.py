@@ -548,3 +548,32 @@ def test_reduce_vector_scalars(hip, oracle, test, null_raft, kernel):
         assert cnt["first_fail_cluster"] == (1 << 64) - 1 and cnt["first_fail_code"] == 0
     for k in COUNTER_KEYS:
         assert cnt[k] == osum[k], (test, k, cnt[k], osum[k])
+
+
+# one batch per set of scenario-only arrays (tests/golden/dev_layout.json holds their layouts)
+RESET_CONFIGS = [
+    ("initial_election_2a", {}), ("reliable_churn_2c", {}), ("unreliable_agree_2c", {}),
+    ("unreliable_3a", {}),
+    ("snapshot_unreliable_recover_concurrent_partition_linearizable_3b",
+     dict(safety=True, trace_clusters=2)),
+    ("multi_4a", {})]
+
+
+def test_reset_equals_fresh_batch(hip):
+    """mr_batch_reset leaves nothing of the last run behind: a batch that ran seed base A to the
+    end, was reset to B and ran again gives the verdict codes, times, digests and counters of a
+    fresh batch of seed base B. An array that reset forgot shows at 64 clusters as at any size."""
+    seed_a, seed_b = _abi.README_SEED, _abi.README_SEED + 4096
+    for test, kw in RESET_CONFIGS:
+        with hip.Batch(test, 64, seed_a, iters=20, **kw) as b:
+            assert b.run()["remaining"] == 0
+            b.reset(seed_b)
+            assert b.run()["remaining"] == 0
+            again, cnt = b.verdicts(), b.counters()
+        with hip.Batch(test, 64, seed_b, iters=20, **kw) as b:
+            assert b.run()["remaining"] == 0
+            fresh, fresh_cnt = b.verdicts(), b.counters()
+        for name, got, want in zip(("code", "time", "digest"), again, fresh):
+            assert np.array_equal(got, want), (test, name, first_diff(got, want))
+        assert cnt == fresh_cnt, (test, {k: (cnt[k], fresh_cnt[k]) for k in cnt
+                                         if cnt[k] != fresh_cnt[k]})
