@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MR_ABI_VERSION 6u
+#define MR_ABI_VERSION 7u
 #define MR_MAX_NODES 8u
 #define MR_MAX_MSG_SLOTS 256u
 #define MR_MAX_AE 32u
@@ -483,7 +483,7 @@ int mr_trace_digests(mr_batch* b, uint32_t k, uint64_t* out, size_t cap, size_t*
  * the real strings (tests/test_kv_trace.py). */
 int mr_trace_applies(mr_batch* b, uint32_t k, uint64_t* out, size_t cap, size_t* n);
 /* ABI 4: the kernel the batch's launches run: "pool_kernel", "step_kernel" or
- * "step_kernel_tape" (keyed decisions or variants set, or decisions recorded) */
+ * "step_kernel_tape" (keyed decisions, variants or a seed list set, or decisions recorded) */
 const char* mr_batch_kernel(const mr_batch* b);
 void mr_batch_destroy(mr_batch* b);
 
@@ -553,6 +553,25 @@ int mr_batch_set_variant_groups(mr_batch* b, const mr_variant_group* groups, siz
                                 const mr_decision* base, size_t n, const mr_decision* edits,
                                 size_t n_edits, const uint32_t* group_of /* [n_clusters] */,
                                 const uint32_t* masks);
+/* ---- seed lists (ABI 7, docs/SEMANTICS.md §12.3) ----
+ * Cluster c runs the seed seed_base + cluster_base + seed_cluster[c] (any order, duplicates
+ * allowed, values need not be < n_clusters). NULL = cluster c runs seed c again. Call after create /
+ * reset and before run. The list is the batch's, not its decision tables': it survives
+ * mr_batch_reset (the same offsets from the new base), mr_batch_submit and mr_batch_set_decisions
+ * (n = 0 too); only NULL here or mr_batch_destroy drops it. While it is set the batch runs
+ * "step_kernel_tape". With MR_F_RECORD the tape of position c is that seed's; with decisions set,
+ * d.cluster is the position and a miss draws from the position's seed. Verdicts, counters,
+ * first_fail_cluster, traces and d.cluster speak of positions, whatever seed runs there. Errors,
+ * which leave the batch as it was: a list on a batch with variants set (and mr_batch_set_variants /
+ * mr_batch_set_variant_groups on a batch with a list), a submitted step not yet finished. */
+int mr_batch_set_seeds(mr_batch* b, const uint32_t* seed_cluster /* [n_clusters] or NULL */);
+/* ABI 7: the recorded tapes of clusters [first, first + count) in one call. drawn[i] (optional) =
+ * decisions cluster first + i drew; off[count + 1] = CSR offsets into out of the records kept,
+ * min(drawn, tape_cap) each, in draw order, cluster = batch position. out == NULL: only drawn and
+ * off are filled (size the buffer, call again). With decisions set instead of MR_F_RECORD: drawn =
+ * misses, off all 0. An error if out != NULL and cap < off[count]. */
+int mr_batch_get_decisions_packed(mr_batch* b, uint32_t first, uint32_t count, uint64_t* drawn,
+                                  uint64_t* off, mr_decision* out, size_t cap);
 /* One cluster of cfg (cluster_base selects the seed for misses) driven by the n decisions:
  * its per-event trace (per-node term / role / commit / applied / last / snapshot after every
  * event), its verdict and verdict time, and (misses != NULL) its draws not in `d`. */

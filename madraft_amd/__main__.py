@@ -4,7 +4,8 @@ analogue of `MADSIM_TEST_SEED=S MADSIM_TEST_NUM=N cargo test <test>`;
 (madraft_amd/trace.py) and prints its verdict; `--seed S --shrink` shrinks a failing seed to a
 1-minimal set of dropped (or delayed) messages (madraft_amd/shrink.py);
 `--clusters N --shrink-failures [K]` runs the N seeds and shrinks the first K failing ones in one
-variant batch of groups, one launch per ddmin round for all of them."""
+variant batch of groups, one launch per ddmin round for all of them; `--seeds LIST` (or `@file`)
+runs exactly those seeds in one batch (docs/SEMANTICS.md §12.3), and with `--shrink` shrinks them."""
 import argparse
 import json
 import time
@@ -33,11 +34,28 @@ def net_mode(test, unreliable_flag):
     return "unreliable" in test
 
 
+def parse_seeds(arg):
+    """`--seeds`: "S1,S2,..." or "@file" with one seed per line (blank lines and # comments
+    skipped); decimal or 0x... numbers, in the order given, duplicates kept."""
+    if arg.startswith("@"):
+        with open(arg[1:]) as f:
+            words = [line.split("#", 1)[0].strip() for line in f]
+    else:
+        words = [w.strip() for w in arg.split(",")]
+    seeds = [int(w, 0) for w in words if w]
+    if not seeds:
+        raise ValueError(f"--seeds {arg!r}: no seeds")
+    return seeds
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("test")
     ap.add_argument("--clusters", type=int, default=None, help="seeds (MADSIM_TEST_NUM)")
     ap.add_argument("--seed", type=int, default=None, help="first seed (MADSIM_TEST_SEED)")
+    ap.add_argument("--seeds", type=parse_seeds, default=None, metavar="LIST",
+                    help="run exactly these seeds in one batch: S1,S2,... or @file (one per line); "
+                         "with --shrink, shrink them")
     ap.add_argument("--nodes", type=int, default=None)
     ap.add_argument("--iters", type=int, default=0)
     ap.add_argument("--unreliable", action="store_true")
@@ -88,7 +106,9 @@ def main():
         # Either way the chosen seeds are shrunk together (shrink_seeds)
         seed = _abi.README_SEED if a.seed is None else a.seed
         chosen = [seed]
-        if not a.shrink:
+        if a.shrink and a.seeds:  # (shrink_seeds wants its first seed to be the smallest)
+            chosen = sorted(a.seeds)
+        elif not a.shrink:
             with sim.Batch(a.test, a.clusters or 1, seed, **cfg_kw) as b:
                 b.run()
                 code = b.verdicts()[0]
@@ -96,6 +116,12 @@ def main():
             chosen = failing[: a.shrink_failures] if a.shrink_failures else failing
         res = shrink.shrink_seeds(a.test, chosen, kinds=tuple(a.shrink_kinds.split(",")), **cfg_kw)
         done = [r for r in res.results if not isinstance(r, str)]
+        if a.seeds and a.shrink:  # one line per seed, in the order given
+            by_seed = dict(zip(chosen, res.results))
+            for s in a.seeds:
+                r = by_seed[s]
+                print(json.dumps({"seed": s, "skipped": r}) if isinstance(r, str) else shrunk_line(s, r))
+            raise SystemExit(0)
         if a.shrink and not done:
             raise sim.SimError(res.results[0].error)
         if a.shrink and a.shrink_tape:
@@ -108,9 +134,12 @@ def main():
                               "kept_sizes": sorted({int(r.kept.size) for r in done})}))
         raise SystemExit(0)
     t0 = time.time()
-    code, _, _, cnt = sim.run_test(a.test, a.seed, a.clusters, nodes=a.nodes, iters=a.iters,
-                                   unreliable=a.unreliable, null_raft=a.null, safety=a.safety,
-                                   flags=flags)
+    if a.seeds:
+        code, _, _, cnt = sim.run_seeds(a.test, a.seeds, **cfg_kw)
+    else:
+        code, _, _, cnt = sim.run_test(a.test, a.seed, a.clusters, nodes=a.nodes, iters=a.iters,
+                                       unreliable=a.unreliable, null_raft=a.null, safety=a.safety,
+                                       flags=flags)
     cnt["wall_s"] = time.time() - t0
     print(json.dumps(cnt))
     raise SystemExit(0 if cnt["failed"] == 0 else 1)

@@ -10,7 +10,7 @@ import re
 
 import numpy as np
 
-MR_ABI_VERSION = 6
+MR_ABI_VERSION = 7
 MR_MAX_NODES = 8
 MR_RUNNING = 0xFFFF
 MR_PASS = 0
@@ -184,4 +184,5 @@ EXPORTS = [
     "mr_trace_digests", "mr_trace_applies", "mr_batch_kernel",  # ABI 4
     "mr_batch_set_variants", "mr_batch_set_variant_masks",  # ABI 5
     "mr_batch_set_variant_groups",  # ABI 6
+    "mr_batch_set_seeds", "mr_batch_get_decisions_packed",  # ABI 7
 ]

@@ -202,7 +202,8 @@ struct Dev {
                     // record: [C][dcap], appended in draw order
   uint32_t* doff;   // replay: [C + 1] row offsets into dtab
   uint32_t dcap;       // record: decisions kept per cluster
-  uint32_t tape_mode;  // 0 Philox, 1 replay keyed decisions, 2 Philox and record them, 3 variants
+  uint32_t tape_mode;  // 0 Philox, 1 replay keyed decisions, 2 Philox and record them, 3 variants,
+                       // 4 Philox from a seed list (sof) and no tables
   // variants (tape_mode 3, SEMANTICS §12.1, §12.2): dtab = the groups' base tapes one after the
   // other, each slice sorted by key; a cluster replays its group's slice, takes its group's edits
   // where its mask row says so, and draws its misses from its group's seed, seed0 + seed_cluster
@@ -242,6 +243,11 @@ struct Dev {
   uint32_t gprobe;  // MR_GUARD builds, MR_GUARD_PROBE set: cluster 0's first delivery reads slot M
   unsigned long long* pcnt;  // pool_kernel: the workgroups' counter sums (64-bit; reduce adds them)
   uint32_t krows;   // the 7-server Raft pool: message slots whose keys live in LDS (the rest in HBM)
+  // a seed list (mr_batch_set_seeds, SEMANTICS §12.3), else null: [C] cluster c draws from the seed
+  // seed0 + sof[c]. Read by the tape kernels' philox() only (tape_mode 1, 2 and 4); the batch's own
+  // allocation beside its decision tables, no row of MR_DEV_ARRAYS: it outlives a reset untouched
+  // and most batches have none
+  const uint32_t* sof;
 };
 // words-pairs per cluster of kwk: the thread slots rounded up to whole 16-B quads (two slots each;
 // slot 0 = the test body and the pad slot hold ~0, so they never win a rescan)

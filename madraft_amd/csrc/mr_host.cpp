@@ -91,6 +91,8 @@ static bool use_pool(uint32_t scn, uint32_t n, uint32_t M) {
 hipError_t launch_reset(const Dev& D, hipStream_t s);
 hipError_t launch_reduce(const Dev& D, unsigned long long* out, uint64_t cluster_base,
                          hipStream_t s);
+hipError_t launch_tape_pack(const uint4* tape, const uint32_t* used, uint32_t dcap, uint32_t first,
+                            uint32_t count, const uint64_t* off, uint32_t* out, hipStream_t s);
 }  // namespace mr
 
 using namespace mr;
@@ -157,6 +159,7 @@ struct mr_batch {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   uint32_t budget = 16384;  // events per cluster per launch (MR_STEP_BUDGET)
   Tables dec;                // the decision tables D draws from (install_tables)
+  uint32_t* sof = nullptr;   // the seed list (mr_batch_set_seeds): the batch's, not its tables'
   bool submitted = false;    // mr_batch_submit enqueued a step not yet finished
   uint32_t kern = 0;         // kernel family of the launches since the reset: 1 pool, 2 step / tape
   std::chrono::steady_clock::time_point t_submit;
@@ -174,6 +177,9 @@ static int copy_trace_row(mr_batch* b, uint32_t k, const T* rows, T* out, size_t
   return 0;
 }
 
+// Dev's tape_mode: the tables' mode, or with a seed list and no tables 4 (Philox, seed list only)
+static uint32_t tape_mode_of(const mr_batch* b) { return b->dec.mode ? b->dec.mode : b->sof ? 4u : 0u; }
+
 // `t` (staged whole by the caller) becomes the batch's decision tables, the previous ones are
 // freed, and the kernels' view of them is published into D
 static void install_tables(mr_batch* b, const Tables& t) {
@@ -182,7 +188,7 @@ static void install_tables(mr_batch* b, const Tables& t) {
   Dev& D = b->D;
   D.dtab = t.tape; D.doff = t.doff; D.dcap = t.dcap;
   D.vdesc = t.vdesc; D.vedit = t.vedit; D.vwords = t.vwords; D.vmask = t.vmask; D.vW = t.vW;
-  D.tape_mode = t.mode;
+  D.tape_mode = tape_mode_of(b);
 }
 
 // A C entry point whose host allocations may throw: an error code across the C ABI, never an
@@ -773,6 +779,7 @@ static int set_variants_impl(mr_batch* b, const mr_variant_group* groups, size_t
 static int variants_enter(mr_batch* b, bool drop) {
   if (!b) return set_err("null batch");
   if (b->cfg.flags & MR_F_RECORD) return set_err("variants on a MR_F_RECORD batch");
+  if (!drop && b->sof) return set_err("variants on a batch with a seed list (mr_batch_set_seeds)");
   HIPCHK(hipSetDevice(b->cfg.device));
   HIPCHK(hipStreamSynchronize(b->stream));
   if (!drop) return 1;
@@ -837,6 +844,46 @@ static int mr_batch_get_decisions_impl(mr_batch* b, uint32_t k, mr_decision* out
   return 0;
 }
 
+// The recorded tapes of clusters [first, first + count): one copy of the CS_TAPE row slice (the row is
+// cluster-minor, so the slice is contiguous), a scan on the host, one tape_pack_kernel launch into a
+// scratch buffer that starts with the offsets, one copy back. The host touches no record.
+static int get_decisions_packed_impl(mr_batch* b, uint32_t first, uint32_t count, uint64_t* drawn,
+                                     uint64_t* off, mr_decision* out, size_t cap) {
+  if (!b || !off) return set_err("null argument");
+  if ((uint64_t)first + count > b->D.C) return set_err("clusters out of range");
+  HIPCHK(hipSetDevice(b->cfg.device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  const uint32_t* used_d = b->D.cs32 + CS_IDX(CS_TAPE, first, b->D.C);
+  std::vector<uint32_t> used(count);
+  if (count) HIPCHK(hipMemcpy(used.data(), used_d, (size_t)count * 4, hipMemcpyDeviceToHost));
+  const bool rec = b->D.tape_mode == 2u;  // (with decisions set the counts are misses: no records)
+  off[0] = 0;
+  for (size_t i = 0; i < count; i++) {
+    if (drawn) drawn[i] = used[i];
+    off[i + 1] = off[i] + (rec ? std::min(used[i], b->D.dcap) : 0u);
+  }
+  const uint64_t total = off[count];
+  if (!out || !total) return 0;
+  if (cap < total)
+    return set_err("mr_batch_get_decisions_packed: out holds " + std::to_string(cap) + " records, " +
+                   std::to_string(total) + " are kept");
+  const size_t head = ((size_t)(count + 1) * sizeof(uint64_t) + 255) & ~size_t(255);
+  char* scratch = nullptr;
+  HIPCHK(hipMalloc(&scratch, head + total * sizeof(mr_decision)));
+  hipError_t e = hipMemcpyAsync(scratch, off, (size_t)(count + 1) * sizeof(uint64_t),
+                                hipMemcpyHostToDevice, b->stream);
+  if (e == hipSuccess)
+    e = launch_tape_pack(b->dec.tape, used_d, b->D.dcap, first, count,
+                         reinterpret_cast<const uint64_t*>(scratch),
+                         reinterpret_cast<uint32_t*>(scratch + head), b->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(out, scratch + head, total * sizeof(mr_decision), hipMemcpyDeviceToHost, b->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+  (void)hipFree(scratch);
+  if (e != hipSuccess) return set_err(std::string("tape pack: ") + hipGetErrorString(e));
+  return 0;
+}
+
 static int mr_replay_impl(const mr_cfg* cfg, const mr_decision* d, size_t n, mr_event* out, size_t cap,
               size_t* n_out, uint16_t* code, uint32_t* time_us, uint64_t* misses) {
   if (!cfg || !n_out) return set_err("null argument");
@@ -887,7 +934,8 @@ void mr_batch_destroy(mr_batch* b) {
 #endif
   if (b->base) (void)hipFree(b->base);
   free_tables(b->dec);
-  // the streaming held-cluster lists belong to the batch, not to its decision tables
+  // the seed list and the streaming held-cluster lists belong to the batch, not to its decision tables
+  if (b->sof) (void)hipFree(b->sof);
   for (uint32_t h = 0; h < 2; h++)
     if (b->held[h]) { (void)hipFree(b->held[h]); b->held[h] = nullptr; }
   if (b->red) (void)hipFree(b->red);
@@ -910,6 +958,36 @@ int mr_batch_verdicts(mr_batch* b, uint16_t* code, uint32_t* time_us, uint64_t* 
 int mr_batch_get_decisions(mr_batch* b, uint32_t k, mr_decision* out, size_t cap, size_t* n) {
   return no_throw("mr_batch_get_decisions",
                   [&] { return mr_batch_get_decisions_impl(b, k, out, cap, n); });
+}
+
+int mr_batch_get_decisions_packed(mr_batch* b, uint32_t first, uint32_t count, uint64_t* drawn,
+                                  uint64_t* off, mr_decision* out, size_t cap) {
+  return no_throw("mr_batch_get_decisions_packed",
+                  [&] { return get_decisions_packed_impl(b, first, count, drawn, off, out, cap); });
+}
+
+// The batch's seed list: uploaded whole before the previous one is freed; the tables stay, and with
+// them their mode (a list alone: mode 4; dropped without tables: the batch's pool / step kernel again)
+int mr_batch_set_seeds(mr_batch* b, const uint32_t* seed_cluster) {
+  if (!b) return set_err("null batch");
+  if (b->submitted) return set_err("batch has a submitted step: mr_batch_finish it first");
+  if (seed_cluster && b->D.tape_mode == 3u)
+    return set_err("a seed list on a batch with variants set");
+  HIPCHK(hipSetDevice(b->cfg.device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  uint32_t* list = nullptr;
+  if (seed_cluster) {
+    const hipError_t e = upload(&list, seed_cluster, (size_t)b->D.C);
+    if (e != hipSuccess) {
+      if (list) (void)hipFree(list);
+      return set_err(std::string("seed list: ") + hipGetErrorString(e));
+    }
+  }
+  if (b->sof) (void)hipFree(b->sof);
+  b->sof = list;
+  b->D.sof = list;
+  b->D.tape_mode = tape_mode_of(b);
+  return 0;
 }
 
 int mr_replay(const mr_cfg* cfg, const mr_decision* d, size_t n, mr_event* out, size_t cap,

@@ -282,7 +282,8 @@ __device__ __forceinline__ uint2 philox2(uint32_t c0, uint32_t c1, uint32_t c2, 
 // in the cluster's sorted table (a miss takes the Philox draw and is counted), record
 // appends {key, words} in draw order, and a variant batch looks the key up in the slice of the
 // one table that the cluster's group owns, takes an edit's words where the cluster's mask says
-// so, and draws its misses from the group's seed.
+// so, and draws its misses from the group's seed. With a seed list set (§12.3) the cluster's seed
+// is the one the list names for its position, in these builds only.
 DI void philox(const Dev& D, X& x, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t& w0,
                uint32_t& w1) {
   uint32_t sc = x.c;  // the seed's cluster: a variant's is its group's seed_cluster
@@ -329,9 +330,9 @@ DI void philox(const Dev& D, X& x, uint32_t c0, uint32_t c1, uint32_t c2, uint32
         }
         CS(CS_TAPE) = CS(CS_TAPE) + 1u;  // no record: the group's seed, whatever x.c (below)
         sc = g.w;
-      } else {
+      } else if (D.tape_mode == 2u) {
         uint4* tb = D.dtab + (size_t)x.c * D.dcap;
-        const uint64_t seed = D.seed0 + x.c;
+        const uint64_t seed = D.seed0 + (D.sof ? D.sof[x.c] : x.c);  // (a seed list: that seed's tape)
         const uint2 w = philox2(c0, c1, c2, (uint32_t)seed, (uint32_t)(seed >> 32));
         w0 = w.x;
         w1 = w.y;
@@ -340,6 +341,9 @@ DI void philox(const Dev& D, X& x, uint32_t c0, uint32_t c1, uint32_t c2, uint32
         if (p < D.dcap) tb[p] = make_uint4(khi, c0, w0, w1);
         return;
       }
+      // a seed list (§12.3; never with variants): a replay's miss, and every draw of a batch with
+      // the list alone (tape_mode 4), takes the draw of the seed the list names for this position
+      if (D.sof) sc = D.sof[x.c];
     }
   }
   const uint64_t seed = D.seed0 + sc;
@@ -850,6 +854,7 @@ DI Dev dev_launder(const Dev& D0) {
   if constexpr (MR_TAPE) {  // a variant batch's tables (null otherwise)
     D.vdesc = glp(D0.vdesc); D.vedit = glp(D0.vedit); D.vwords = glp(D0.vwords);
     D.vmask = glp(D0.vmask);
+    D.sof = glp(D0.sof);  // a seed list (null otherwise)
   }
   return D;
 }
@@ -2409,6 +2414,42 @@ __global__ void __launch_bounds__(256) reduce_kernel(Dev D, unsigned long long* 
     if (cnt_is_max(i) && i < CNT__N) atomicMax(&out[i], acc[i]);
     else atomicAdd(&out[i], acc[i]);
   }
+}
+
+// mr_batch_get_decisions_packed: the used prefixes of the record tape's rows ([C][dcap] 16-B
+// records {stream << 16 | entity, seq, w0, w1}) of clusters [first, first + count), gathered into
+// finished 20-B mr_decision records {cluster, stream | entity << 16, seq, w0, w1} at the 64-bit CSR
+// offsets the host scanned. One block per cluster, its lanes over the cluster's output dwords: a
+// wave stores 64 consecutive dwords and reads the words of the 13 or 14 consecutive 16-B records
+// they come from. No atomics: every output dword has one writer. A cluster's bound is min(drawn, dcap) as the device holds it, and never past its CSR row.
+constexpr uint32_t PACK_BLOCK = 256, DEC_W = sizeof(mr_decision) / 4u;
+static_assert(sizeof(mr_decision) == 20 && DEC_W == 5, "mr_decision is five dwords");
+__global__ void __launch_bounds__(PACK_BLOCK) tape_pack_kernel(const uint4* tape, const uint32_t* used,
+                                                               uint32_t dcap, uint32_t first,
+                                                               uint32_t count, const uint64_t* off,
+                                                               uint32_t* out) {
+  for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+    const uint32_t c = first + i;
+    const uint64_t o = off[i], room = off[i + 1] - o;
+    uint64_t m = used[i] < dcap ? used[i] : dcap;
+    if (m > room) m = room;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(tape + (size_t)c * dcap);
+    uint32_t* dst = out + o * DEC_W;
+    for (uint64_t j = threadIdx.x; j < m * DEC_W; j += PACK_BLOCK) {
+      const uint64_t r = j / DEC_W;
+      const uint32_t f = (uint32_t)(j - r * DEC_W);
+      uint32_t v = c;  // word 0: the batch position
+      if (f) v = src[r * 4u + (f - 1u)];
+      if (f == 1u) v = (v >> 16) | (v << 16);  // stream in the low half, entity in the high
+      dst[j] = v;
+    }
+  }
+}
+hipError_t launch_tape_pack(const uint4* tape, const uint32_t* used, uint32_t dcap, uint32_t first,
+                            uint32_t count, const uint64_t* off, uint32_t* out, hipStream_t s) {
+  dim3 blk(PACK_BLOCK), grd(count < (1u << 20) ? count : (1u << 20));
+  hipLaunchKernelGGL(tape_pack_kernel, grd, blk, 0, s, tape, used, dcap, first, count, off, out);
+  return hipGetLastError();
 }
 
 hipError_t launch_reset(const Dev& D, hipStream_t s) {

@@ -226,7 +226,7 @@ def shrink_seed(test, seed, kinds=("drop",), tape_cap=1 << 16, **cfg_kw):
     """Shrink the failing run of `test` at `seed` (make_cfg's keywords: iters, flags, ...) to a
     1-minimal set of faults of `kinds` on the GPU: shrink_seeds' one-seed case — one record run,
     one variant batch of n_variants(base, kinds) clusters, one launch per ddmin round, one
-    mr_replay of the minimal tape. A seed that passes, or draws more than tape_cap decisions, is a
+    replay of the minimal tape. A seed that passes, or draws more than tape_cap decisions, is a
     SimError.
 
     Returns ShrunkSeed: kept (the base records of the faults that stay, DECISION_DTYPE), their
@@ -252,16 +252,25 @@ class NotShrunk(str):
         return self
 
 
-def shrink_seeds(test, seeds, kinds=("drop",), tape_cap=1 << 16, **cfg_kw):
+def _chunks(n, size):
+    """range(n) cut into consecutive runs of at most `size` (at least 1) items."""
+    size = max(1, int(size))
+    return [range(i, min(n, i + size)) for i in range(0, n, size)]
+
+
+def shrink_seeds(test, seeds, kinds=("drop",), tape_cap=1 << 16, record_bytes=1 << 32, **cfg_kw):
     """Shrink the failing runs of `test` at every seed of `seeds` at once (docs/SEMANTICS.md
-    §12.2; make_cfg's keywords: iters, flags, ...), each to a 1-minimal set of faults of `kinds`:
-    each seed is recorded (one 1-cluster MR_F_RECORD batch, reset to seed after seed), then one
-    variant batch holds a group per failing seed — group g owns a contiguous run of
-    n_variants(its base, kinds) clusters — and every round of shrink_many is one
+    §12.2, §12.3; make_cfg's keywords: iters, flags, ...), each to a 1-minimal set of faults of
+    `kinds`, in three batches whatever the number of seeds: every seed is recorded in one
+    MR_F_RECORD batch over the seed list (Batch.set_seeds) and read back at once
+    (Batch.decisions_all); then one variant batch holds a group per failing seed — group g owns a
+    contiguous run of n_variants(its base, kinds) clusters — and every round of shrink_many is one
     set_variant_masks + reset + run of it: the launches are the longest seed's rounds, not their
     sum. The clusters a group's round does not use, and all of a finished group's, repeat its
-    candidate 0 and their verdicts are ignored. Each minimal tape is replayed (mr_replay) and
-    must give the seed's verdict.
+    candidate 0 and their verdicts are ignored. Every minimal tape is replayed in one batch
+    (sim.replay_many) and must give its seed's verdict. Memory stays bounded: a record batch holds
+    at most record_bytes // (tape_cap * 16) seeds and a replay batch record_bytes // (trace_cap *
+    32) (trace_cap: cfg_kw's, default 2^16), so more seeds than that take several of each.
 
     Returns SeedsShrunk(results, launches): results[i] is the ShrunkSeed of seeds[i], or, for a
     seed that is not shrunk, the string (NotShrunk) "passes" or "tape_cap" (it drew more than
@@ -276,23 +285,27 @@ def shrink_seeds(test, seeds, kinds=("drop",), tape_cap=1 << 16, **cfg_kw):
     seed_base = seeds[0] - base_c  # the variant batch's; group g's seed_cluster = its seed - seeds[0]
     if min(seeds) < seeds[0] or max(seeds) - seeds[0] >= 1 << 32:
         raise sim.SimError("shrink_seeds: seeds[0] must be the smallest, the others within 2^32 of it")
+    trace_cap = int(cfg_kw.pop("trace_cap", None) or 1 << 16)
     live, bases, targets = [], [], []
-    with sim.Batch(test, 1, seed_base, cluster_base=base_c, flags=flags | _abi.MR_F_RECORD,
-                   tape_cap=tape_cap, **cfg_kw) as b:
-        for i, s in enumerate(seeds):
-            if i:  # (the batch starts at seeds[0])
-                b.reset(s - base_c)
+    for chunk in _chunks(len(seeds), int(record_bytes) // (int(tape_cap) * 16)):
+        with sim.Batch(test, len(chunk), seed_base, cluster_base=base_c,
+                       flags=flags | _abi.MR_F_RECORD, tape_cap=tape_cap, **cfg_kw) as b:
+            b.set_seeds([seeds[i] for i in chunk])
             b.run()
-            code = int(b.verdicts()[0][0])
-            n, base = b.decisions(0, tape_cap)
+            codes = b.verdicts()[0]
+            drawn, off, rec = b.decisions_all()
+        for k, i in enumerate(chunk):
+            code, n = int(codes[k]), int(drawn[k])
             if code == _abi.MR_PASS or n > tape_cap:
                 results[i] = NotShrunk(
                     "passes" if code == _abi.MR_PASS else "tape_cap",
                     f"tape_cap {tape_cap} too small: the seed draws {n} decisions" if n > tape_cap
-                    else f"seed {s} passes {test}: nothing to shrink")
+                    else f"seed {seeds[i]} passes {test}: nothing to shrink")
                 continue
+            base = rec[int(off[k]): int(off[k + 1])].copy()
+            base["cluster"] = 0  # (a tape names no position: what a 1-cluster recording gives)
             live.append(i)
-            bases.append(base.copy())
+            bases.append(base)
             targets.append(code)
     if not live:
         return SeedsShrunk(results, 0)
@@ -326,13 +339,15 @@ def shrink_seeds(test, seeds, kinds=("drop",), tape_cap=1 << 16, **cfg_kw):
             return {g: code[first[g]: first[g] + applied.shape[0]] for g, applied in rows.items()}
 
         passes, _ = shrink_many(evaluate_groups, bases, kinds, targets)
-    for i, bs, target, p in zip(live, bases, targets, passes):
-        tape = apply_edits(bs, p.idx, p.edits, p.applied)
-        tr, code, _, _ = sim.replay(test, tape, seed=seeds[i] - base_c, cluster_base=base_c,
-                                    flags=flags, **cfg_kw)
-        if code != target:
-            raise sim.SimError(f"seed {seeds[i]}: the minimal tape replays to verdict {code}, "
-                               f"not {target}")
-        results[i] = ShrunkSeed(bs[p.idx[p.kept]], p.kind, target, tr, tape, p.faults, p.rounds,
-                                p.candidates)
+    tapes = [apply_edits(bs, p.idx, p.edits, p.applied) for bs, p in zip(bases, passes)]
+    for chunk in _chunks(len(live), int(record_bytes) // (trace_cap * 32)):
+        played = sim.replay_many(test, [tapes[g] for g in chunk], [seeds[live[g]] for g in chunk],
+                                 trace_cap=trace_cap, cluster_base=base_c, flags=flags, **cfg_kw)
+        for g, (tr, code, _, _) in zip(chunk, played):
+            i, bs, target, p = live[g], bases[g], targets[g], passes[g]
+            if code != target:
+                raise sim.SimError(f"seed {seeds[i]}: the minimal tape replays to verdict {code}, "
+                                   f"not {target}")
+            results[i] = ShrunkSeed(bs[p.idx[p.kept]], p.kind, target, tr, tapes[g], p.faults,
+                                    p.rounds, p.candidates)
     return SeedsShrunk(results, launches)

@@ -63,6 +63,9 @@ def lib():
     L.mr_batch_set_variant_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                               C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                               C.c_void_p]
+    L.mr_batch_set_seeds.argtypes = [C.c_void_p, C.c_void_p]
+    L.mr_batch_get_decisions_packed.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_size_t]
     L.mr_decision_word.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     L.mr_decision_word.restype = C.c_uint32
     L.mr_replay.argtypes = [C.POINTER(MrCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
@@ -147,6 +150,19 @@ def _records(d):
     return a, _ptr(a)
 
 
+def seed_offsets(seeds, seed_base, cluster_base=0):
+    """The seed list of mr_batch_set_seeds for the absolute `seeds`: uint32 offsets from seed_base +
+    cluster_base (docs/SEMANTICS.md §12.3). A seed below that base, or 2^32 or more above it, is a
+    SimError."""
+    base = int(seed_base) + int(cluster_base)
+    off = [int(s) - base for s in seeds]
+    for s, o in zip(seeds, off):
+        if not 0 <= o < 1 << 32:
+            raise SimError(f"seed {int(s)} is not within [0, 2^32) of the base {base} "
+                           f"(seed_base {int(seed_base)} + cluster_base {int(cluster_base)})")
+    return np.array(off, np.uint32)
+
+
 class Batch:
     """`clusters` seeds of one reference test, resident on one GPU."""
 
@@ -207,6 +223,17 @@ class Batch:
         c = MrCounters()
         _check(lib().mr_batch_counters(self._b, C.byref(c)))
         return c.to_dict()
+
+    def set_seeds(self, seeds):
+        """Position c runs the absolute seed seeds[c] (mr_batch_set_seeds; any order, duplicates
+        allowed, each within 2^32 above seed_base + cluster_base); None = seed c again. The list
+        stays through reset() (the same offsets from the new base) and set_decisions()."""
+        off = None
+        if seeds is not None:
+            off = seed_offsets(seeds, self.cfg.seed_base, self.cfg.cluster_base)
+            if off.shape != (self.clusters,):
+                raise SimError(f"seeds: shape {off.shape}, not ({self.clusters},)")
+        _check(lib().mr_batch_set_seeds(self._b, off.ctypes.data if off is not None else None))
 
     def _set_tables(self, rc, n_edits=0):
         """After a call that replaces or drops the decision tables: `n_edits` = the mask columns
@@ -289,6 +316,22 @@ class Batch:
         _check(lib().mr_batch_get_decisions(self._b, int(k), out.ctypes.data, cap, C.byref(n)))
         return int(n.value), out[: min(n.value, cap)]
 
+    def decisions_all(self, first=0, count=None):
+        """(drawn, off, records) of clusters [first, first + count) in one read-back
+        (mr_batch_get_decisions_packed): drawn[i] = decisions cluster first + i drew (with decisions
+        set: its misses), records[off[i]: off[i + 1]] = those MR_F_RECORD kept, min(drawn, tape_cap)
+        of them in draw order, cluster = the batch position."""
+        count = self.clusters - int(first) if count is None else int(count)
+        drawn = np.zeros(count, np.uint64)
+        off = np.zeros(count + 1, np.uint64)
+        f = lib().mr_batch_get_decisions_packed
+        _check(f(self._b, int(first), count, _ptr(drawn), off.ctypes.data, None, 0))
+        rec = np.empty(int(off[-1]), DECISION_DTYPE)
+        if rec.size:
+            _check(f(self._b, int(first), count, _ptr(drawn), off.ctypes.data, rec.ctypes.data,
+                     rec.size))
+        return drawn, off, rec
+
     def trace(self, k, cap=None):
         cap = cap or int(self.cfg.trace_cap)
         out = np.empty(cap, EVENT_DTYPE)
@@ -315,7 +358,7 @@ class Batch:
     @property
     def kernel(self):
         """mr_batch_kernel: "pool_kernel", "step_kernel" or "step_kernel_tape" (decisions,
-        variants or recording)."""
+        variants, a seed list or recording)."""
         return lib().mr_batch_kernel(self._b).decode()
 
 
@@ -332,6 +375,70 @@ def replay(test, decisions, trace_cap=1 << 16, cluster_base=0, **kw):
     return out[: n.value], int(code.value), int(tm.value), int(ms.value)
 
 
+# a key no draw has (mr_replay's): a cluster with this one record replays an empty tape, every draw
+# a counted miss
+_NO_DRAW = (_abi.MR_DS_TESTER, 0xFFFF, 0xFFFFFFFF, 0, 0)
+
+
+def replay_many(test, tapes, seeds, trace_cap=1 << 16, **kw):
+    """replay() of tapes[i] at the absolute seed seeds[i], for every i in one batch: position i
+    runs seeds[i] (set_seeds) driven by tapes[i] (one set_decisions, cluster = position) and keeps
+    a trace. A list of (trace, code, time_us, misses), element i what
+    replay(test, tapes[i], seed=seeds[i] - cluster_base, ...) returns."""
+    seeds = [int(s) for s in seeds]
+    if len(tapes) != len(seeds):
+        raise SimError(f"replay_many: {len(tapes)} tapes for {len(seeds)} seeds")
+    if not seeds:
+        return []
+    kw = dict(kw)
+    kw.pop("seed", None)
+    base_c = int(kw.pop("cluster_base", 0))
+    flags = int(kw.pop("flags", 0)) & ~_abi.MR_F_RECORD
+    rows = []
+    for i, t in enumerate(tapes):
+        d = np.array(_records(t)[0])
+        if not d.size:
+            d = np.zeros(1, DECISION_DTYPE)
+            d[0] = (0,) + _NO_DRAW
+        d["cluster"] = i
+        rows.append(d)
+    with Batch(test, len(seeds), min(seeds) - base_c, cluster_base=base_c, flags=flags,
+               trace_clusters=len(seeds), trace_cap=trace_cap, **kw) as b:
+        b.set_seeds(seeds)
+        b.set_decisions(np.concatenate(rows))
+        b.run()
+        code, tm, _ = b.verdicts()
+        misses = b.decisions_all()[0]
+        return [(b.trace(i, trace_cap), int(code[i]), int(tm[i]), int(misses[i]))
+                for i in range(len(seeds))]
+
+
+def _print_failures(test, code, t, seed_of):
+    """The first failures like the #[madsim::test] harness (README.md:44-48); seed_of(k) = the seed
+    position k ran."""
+    for k in np.nonzero(code != _abi.MR_PASS)[0][:3]:
+        print(f"---- {test} ----\npanicked at '{fail_message(code[k])}' "
+              f"({FAIL_NAMES.get(int(code[k]), code[k])}, t={t[k] * 1e-6:.3f}s)\n"
+              f"MADSIM_TEST_SEED={seed_of(int(k))}")
+
+
+def run_seeds(test, seeds, **kw):
+    """run_test for a list of absolute seeds: one batch of len(seeds) clusters with seed_base =
+    min(seeds) - cluster_base, position i running seeds[i] (set_seeds). Returns (codes, times_us,
+    digests, counters) by position; failures are printed with their own MADSIM_TEST_SEED."""
+    seeds = [int(s) for s in seeds]
+    if not seeds:
+        raise SimError("run_seeds: no seeds")
+    base_c = int(kw.pop("cluster_base", 0))
+    with Batch(test, len(seeds), min(seeds) - base_c, cluster_base=base_c, **kw) as b:
+        b.set_seeds(seeds)
+        b.run()
+        code, t, dig = b.verdicts()
+        cnt = b.counters()
+    _print_failures(test, code, t, lambda k: seeds[k])
+    return code, t, dig, cnt
+
+
 def run_test(test, seed=None, num=None, **kw):
     """`MADSIM_TEST_SEED=seed MADSIM_TEST_NUM=num cargo test <test>` on the GPU.
 
@@ -344,9 +451,5 @@ def run_test(test, seed=None, num=None, **kw):
         b.run()
         code, t, dig = b.verdicts()
         cnt = b.counters()
-    bad = np.nonzero(code != _abi.MR_PASS)[0]
-    for k in bad[:3]:
-        print(f"---- {test} ----\npanicked at '{fail_message(code[k])}' "
-              f"({FAIL_NAMES.get(int(code[k]), code[k])}, t={t[k] * 1e-6:.3f}s)\n"
-              f"MADSIM_TEST_SEED={seed + int(b.cfg.cluster_base) + int(k)}")
+    _print_failures(test, code, t, lambda k: seed + int(b.cfg.cluster_base) + k)
     return code, t, dig, cnt
