@@ -181,6 +181,15 @@ struct alignas(16) SE {
   uint32_t mask, term;
 };
 
+// Dev::tape_mode (SEMANTICS §12): what a draw does in the decision-tape kernels, which run whenever
+// it is not TAPE_OFF. Whatever the mode, the draw's seed is the one seed rule of philox()
+enum TapeMode : uint32_t {
+  TAPE_OFF = 0,  // Philox from the cluster's own seed: the pool / step kernels
+  TAPE_LOOKUP,   // look the key up in my slice (replay, variants); a miss is counted and drawn
+  TAPE_RECORD,   // draw and append {key, words} to my tape
+  TAPE_SEEDS     // only take my seed from the list (no tables)
+};
+
 // ---- everything the kernels see (passed by value as a kernel argument)
 struct Dev {
   // config
@@ -198,19 +207,23 @@ struct Dev {
   uint32_t* kvs32;  // persisted KV snapshots (maxraftstate)
   uint32_t* kring;  // recent KV snapshots by index (maxraftstate)
   uint4* dtab;      // keyed decisions {stream << 16 | entity, seq, w0, w1}, else null:
-                    // replay: CSR rows, cluster c's sorted by key at [doff[c], doff[c + 1]);
+                    // lookup: the groups' tapes one after the other, each slice sorted by key;
                     // record: [C][dcap], appended in draw order
-  uint32_t* doff;   // replay: [C + 1] row offsets into dtab
+  // a seed list (mr_batch_set_seeds, SEMANTICS §12.3), else null: [C] cluster c draws from the seed
+  // seed0 + sof[c]. Read by the tape kernels' philox() only; the batch's own allocation beside its
+  // decision tables, no row of MR_DEV_ARRAYS: it outlives a reset untouched and most batches have none
+  const uint32_t* sof;
   uint32_t dcap;       // record: decisions kept per cluster
-  uint32_t tape_mode;  // 0 Philox, 1 replay keyed decisions, 2 Philox and record them, 3 variants,
-                       // 4 Philox from a seed list (sof) and no tables
-  // variants (tape_mode 3, SEMANTICS §12.1, §12.2): dtab = the groups' base tapes one after the
-  // other, each slice sorted by key; a cluster replays its group's slice, takes its group's edits
-  // where its mask row says so, and draws its misses from its group's seed, seed0 + seed_cluster
+  uint32_t tape_mode;  // a TapeMode: what a draw of the tape kernels does (0: the pool / step kernels run)
+  // lookup (TAPE_LOOKUP, SEMANTICS §12 - §12.2): a cluster looks its draws up in its group's slice of
+  // dtab, takes its group's edits where its mask row says so, and draws its misses from its group's
+  // seed, seed0 + seed_cluster. Replay is a variant batch of C one-cluster groups without edits:
+  // cluster c's slice is its row, its seed_cluster is c, and vedit, vwords, vmask are null, vW 0
   // (mr_batch_set_variants: one group, slice = the table, seed_cluster 0)
-  uint4* vdesc;     // [C] the cluster's group: {slice offset, slice records, its first edit in
-                    // vwords, seed_cluster} (one load per draw, no group_of -> groups indirection)
-  uint32_t* vedit;  // [records] the base record's edit within its group, ~0u = none
+  uint4* tdesc;     // [C] the cluster's group: {slice offset, slice records (0: every draw misses),
+                    // its first edit in vwords, seed_cluster} (one load per draw, no group_of ->
+                    // groups indirection)
+  uint32_t* vedit;  // [records] the record's edit within its group, ~0u = none; null: no record has one
   uint2* vwords;    // [edits] an edit's replacement words (w0, w1), the groups' one after the other
   uint32_t* vmask;  // [C][vW] bit j of cluster c's row: c takes its group's edit j
   uint32_t vW;      // mask words per cluster = ceil(the widest group's edits / 32)
@@ -243,11 +256,6 @@ struct Dev {
   uint32_t gprobe;  // MR_GUARD builds, MR_GUARD_PROBE set: cluster 0's first delivery reads slot M
   unsigned long long* pcnt;  // pool_kernel: the workgroups' counter sums (64-bit; reduce adds them)
   uint32_t krows;   // the 7-server Raft pool: message slots whose keys live in LDS (the rest in HBM)
-  // a seed list (mr_batch_set_seeds, SEMANTICS §12.3), else null: [C] cluster c draws from the seed
-  // seed0 + sof[c]. Read by the tape kernels' philox() only (tape_mode 1, 2 and 4); the batch's own
-  // allocation beside its decision tables, no row of MR_DEV_ARRAYS: it outlives a reset untouched
-  // and most batches have none
-  const uint32_t* sof;
 };
 // words-pairs per cluster of kwk: the thread slots rounded up to whole 16-B quads (two slots each;
 // slot 0 = the test body and the pad slot hold ~0, so they never win a rescan)

@@ -113,22 +113,25 @@ int set_err(const std::string& s) {
 
 constexpr uint32_t STEP_LANES = 64;  // lanes per step-kernel block (one wave)
 
-// A batch's decision tables on the device, each its own allocation, whoever made them: replay
-// rows and offsets (set_decisions_impl), the record tape (MR_F_RECORD), or a variant batch's base
-// tapes, descriptors, edits and masks (set_variants_impl). All null: Philox draws.
+// who installed a batch's decision tables: what the lifetime rules ask (variants_enter drops only a
+// variant's, a seed list and variants exclude each other, set_variant_masks needs a variant's)
+enum Owner : uint32_t { OWN_NONE, OWN_REPLAY, OWN_RECORD, OWN_VARIANTS };
+
+// A batch's decision tables on the device, each its own allocation, whoever made them: the record
+// tape (MR_F_RECORD), or what stage_slices built, the sorted slices and the clusters' descriptors
+// of a replay, and with them a variant batch's edits and masks. All null: Philox draws.
 struct Tables {
-  uint4* tape = nullptr;      // keyed decisions: replay rows, the record tape, the groups' base tapes
-  uint32_t* doff = nullptr;   // replay: CSR row offsets of `tape`
-  uint4* vdesc = nullptr;     // variants: the clusters' group descriptors,
-  uint32_t* vedit = nullptr;  // the base records' edit indices within their group,
+  uint4* tape = nullptr;      // keyed decisions: the record tape, or the groups' sorted slices
+  uint4* tdesc = nullptr;     // slices: the clusters' group descriptors;
+  uint32_t* vedit = nullptr;  // variants: the base records' edit indices within their group,
   uint2* vwords = nullptr;    // the edits' words,
   uint32_t* vmask = nullptr;  // and the clusters' mask rows (set_variant_masks rewrites them)
-  uint32_t dcap = 0, vW = 0, mode = 0;  // Dev's dcap, vW and tape_mode with these tables
+  uint32_t dcap = 0, vW = 0;  // Dev's dcap and vW with these tables
+  Owner mode = OWN_NONE;
 };
 
 void free_tables(Tables& t) {
-  for (void* p : {(void*)t.tape, (void*)t.doff, (void*)t.vdesc, (void*)t.vedit, (void*)t.vwords,
-                  (void*)t.vmask})
+  for (void* p : {(void*)t.tape, (void*)t.tdesc, (void*)t.vedit, (void*)t.vwords, (void*)t.vmask})
     if (p) (void)hipFree(p);
   t = Tables{};
 }
@@ -177,8 +180,11 @@ static int copy_trace_row(mr_batch* b, uint32_t k, const T* rows, T* out, size_t
   return 0;
 }
 
-// Dev's tape_mode: the tables' mode, or with a seed list and no tables 4 (Philox, seed list only)
-static uint32_t tape_mode_of(const mr_batch* b) { return b->dec.mode ? b->dec.mode : b->sof ? 4u : 0u; }
+// Dev's tape_mode: what a draw does with the owner's tables, or with a seed list and no tables
+static TapeMode tape_mode_of(const mr_batch* b) {
+  if (b->dec.mode == OWN_RECORD) return TAPE_RECORD;
+  return b->dec.mode != OWN_NONE ? TAPE_LOOKUP : b->sof ? TAPE_SEEDS : TAPE_OFF;
+}
 
 // `t` (staged whole by the caller) becomes the batch's decision tables, the previous ones are
 // freed, and the kernels' view of them is published into D
@@ -186,8 +192,8 @@ static void install_tables(mr_batch* b, const Tables& t) {
   free_tables(b->dec);
   b->dec = t;
   Dev& D = b->D;
-  D.dtab = t.tape; D.doff = t.doff; D.dcap = t.dcap;
-  D.vdesc = t.vdesc; D.vedit = t.vedit; D.vwords = t.vwords; D.vmask = t.vmask; D.vW = t.vW;
+  D.dtab = t.tape; D.dcap = t.dcap;
+  D.tdesc = t.tdesc; D.vedit = t.vedit; D.vwords = t.vwords; D.vmask = t.vmask; D.vW = t.vW;
   D.tape_mode = tape_mode_of(b);
 }
 
@@ -316,7 +322,7 @@ static int mr_batch_create_impl(const mr_cfg* cfg, mr_batch** out) {
       return set_err(std::string("tape allocation failed: ") + hipGetErrorString(e));
     }
     t.dcap = cfg->tape_cap;
-    t.mode = 2;
+    t.mode = OWN_RECORD;
     install_tables(b, t);
   }
   if (hipMemset(b->D.prof, 0, PROF_SLOTS * sizeof(unsigned long long)) != hipSuccess ||
@@ -633,8 +639,7 @@ uint32_t mr_decision_word(uint32_t v, uint32_t lo, uint32_t hi) {
   return (uint32_t)((num + span - 1) / span);
 }
 
-// the batch's decision tables (replay rows + offsets, the record tape, or a variant batch's
-// base tape, edits and masks) freed; Philox draws
+// the batch's decision tables (whoever installed them) freed; Philox draws
 static void drop_decisions(mr_batch* b) { install_tables(b, Tables{}); }
 
 // `t`, staged by a chain of upload()s that ended with `e`: installed, or on an error freed, the
@@ -648,39 +653,112 @@ static int install_staged(mr_batch* b, Tables& t, hipError_t e, const char* what
   return 0;
 }
 
-// Keyed decisions as CSR rows: every decision once (16 B each) plus C + 1 offsets, so the
-// table is O(n + C) whatever the longest row. Everything is validated and staged before the
-// previous table is dropped, so a rejected call leaves the batch as it was.
+// (a variant batch's messages name the group only where there are groups)
+static std::string in_group(bool many, size_t g) {
+  return many ? " (group " + std::to_string(g) + ")" : std::string();
+}
+
+// The lookup tables of mr_batch_set_decisions, mr_batch_set_variants and mr_batch_set_variant_groups:
+// the groups' base tapes base[base_off .. +n_base) one after the other, each slice packed, sorted
+// once and checked for duplicate keys, and one 16-B descriptor per cluster copied from its group.
+// Replay (`who` = OWN_REPLAY) is a variant batch of C one-cluster groups without edits: cluster c is
+// in group c, and no edit array exists. A variant batch's cluster c is in group group_of[c] (null:
+// group 0); it has each base record's edit index within its group beside it, the edits' words in
+// group order, and one mask row per cluster. The groups' ranges are the caller's to check.
+// Validated and staged whole before the previous tables are dropped, so a rejected call leaves the
+// batch as it was.
+static int stage_slices(mr_batch* b, Owner who, const mr_variant_group* groups, size_t n_groups,
+                        const mr_decision* base, const mr_decision* edits, const uint32_t* group_of,
+                        const uint32_t* masks) {
+  const size_t C = b->D.C;
+  const bool replay = who == OWN_REPLAY, many = !replay && group_of != nullptr;
+  size_t rows = 0, words = 0, widest = 0;
+  for (size_t g = 0; g < n_groups; g++) {
+    rows += groups[g].n_base;
+    words += groups[g].n_edits;
+    if (groups[g].n_edits > widest) widest = groups[g].n_edits;
+  }
+  if (rows >= (1ull << 32) || words >= (1ull << 32))
+    return set_err("too many decisions for one batch (2^32 - 1 at most)");
+  auto key_of = [](const mr_decision& r) { return make_uint2(((uint32_t)r.stream << 16) | r.entity, r.seq); };
+  auto bad_stream = [](const mr_decision& r) { return r.stream < MR_DS_TESTER || r.stream > MR_DS_NET; };
+  auto lt = [](const uint4& a, const uint4& c) { return a.x < c.x || (a.x == c.x && a.y < c.y); };
+  std::vector<uint4> tab(rows), desc(n_groups);
+  std::vector<uint32_t> ved(replay ? 0 : rows, ~0u);
+  std::vector<uint2> vw(words);
+  size_t r0 = 0, w0 = 0;  // the group's first row of tab / ved, its first edit of vw
+  for (size_t g = 0; g < n_groups; g++) {
+    const mr_variant_group& G = groups[g];
+    uint4* row = tab.data() + r0;
+    for (size_t i = 0; i < G.n_base; i++) {
+      const mr_decision& r = base[G.base_off + i];
+      if (bad_stream(r)) return set_err("bad decision stream" + in_group(many, g));
+      const uint2 k = key_of(r);
+      row[i] = make_uint4(k.x, k.y, r.w0, r.w1);
+    }
+    std::sort(row, row + G.n_base, lt);
+    for (size_t k = 1; k < G.n_base; k++)
+      if (row[k].x == row[k - 1].x && row[k].y == row[k - 1].y)
+        return set_err(replay ? "duplicate decision key (cluster " + std::to_string(g) + ")"
+                              : "duplicate decision key in the base tape" + in_group(many, g));
+    for (size_t j = 0; j < G.n_edits; j++) {
+      const mr_decision& r = edits[G.edit_off + j];
+      if (bad_stream(r)) return set_err("bad decision stream (edit " + std::to_string(j) + ")" + in_group(many, g));
+      const uint2 k = key_of(r);
+      const uint4* it = std::lower_bound(row, row + G.n_base, make_uint4(k.x, k.y, 0, 0), lt);
+      if (it == row + G.n_base || it->x != k.x || it->y != k.y)
+        return set_err("edit " + std::to_string(j) + ": its key is not in the base tape" + in_group(many, g));
+      uint32_t& e = ved[r0 + (it - row)];
+      if (e != ~0u)
+        return set_err("duplicate edit key (edits " + std::to_string(e) + " and " + std::to_string(j) + ")" +
+                       in_group(many, g));
+      e = (uint32_t)j;
+      vw[w0 + j] = make_uint2(r.w0, r.w1);
+    }
+    desc[g] = make_uint4((uint32_t)r0, G.n_base, (uint32_t)w0, G.seed_cluster);
+    r0 += G.n_base;
+    w0 += G.n_edits;
+  }
+  std::vector<uint4> cdesc(C);
+  for (size_t c = 0; c < C; c++) cdesc[c] = desc[replay ? c : many ? group_of[c] : 0];
+  const size_t W = (widest + 31) / 32;
+  Tables t;
+  t.vW = (uint32_t)W;
+  t.mode = who;
+  hipError_t e = upload(&t.tape, tab.data(), rows);
+  if (e == hipSuccess) e = upload(&t.tdesc, cdesc.data(), C);
+  if (!replay) {  // (null in a replay: no record has an edit)
+    if (e == hipSuccess) e = upload(&t.vedit, ved.data(), rows);
+    if (e == hipSuccess) e = upload(&t.vwords, vw.data(), words);
+    if (e == hipSuccess) e = upload(&t.vmask, masks, C * W);
+  }
+  return install_staged(b, t, e, replay ? "decision table" : "variant tables");
+}
+
+// Keyed decisions in any order: a counting sort by cluster makes cluster c's records the base tape
+// of group c, whose seed_cluster is c and which has no edits (a row may be empty: every draw of
+// that cluster misses). The table is O(n + C) whatever the longest row.
 static int set_decisions_impl(mr_batch* b, const mr_decision* d, size_t n) {
   const size_t C = b->D.C;
   if (n >= (1ull << 32)) return set_err("too many decisions for one batch (2^32 - 1 at most)");
-  std::vector<uint32_t> off(C + 1, 0);
+  std::vector<mr_variant_group> rows(C);  // (value-initialised: zeros)
   for (size_t i = 0; i < n; i++) {
     if (d[i].cluster >= C) return set_err("decision for a cluster outside the batch");
-    if (d[i].stream < MR_DS_TESTER || d[i].stream > MR_DS_NET) return set_err("bad decision stream");
-    off[d[i].cluster + 1]++;
+    rows[d[i].cluster].n_base++;
   }
-  for (size_t c = 0; c < C; c++) off[c + 1] += off[c];
-  std::vector<uint4> tab(n);
-  std::vector<uint32_t> fill(off.begin(), off.end() - 1);
+  uint32_t at = 0;
+  for (size_t c = 0; c < C; c++) {  // (n_base counts again below, as the row's fill)
+    rows[c].seed_cluster = (uint32_t)c;
+    rows[c].base_off = at;
+    at += rows[c].n_base;
+    rows[c].n_base = 0;
+  }
+  std::vector<mr_decision> tab(n);
   for (size_t i = 0; i < n; i++) {
-    const mr_decision& r = d[i];
-    tab[fill[r.cluster]++] = make_uint4(((uint32_t)r.stream << 16) | r.entity, r.seq, r.w0, r.w1);
+    mr_variant_group& G = rows[d[i].cluster];
+    tab[G.base_off + G.n_base++] = d[i];
   }
-  auto lt = [](const uint4& a, const uint4& c) { return a.x < c.x || (a.x == c.x && a.y < c.y); };
-  for (size_t c = 0; c < C; c++) {
-    uint4* row = tab.data() + off[c];
-    const uint32_t cnt = off[c + 1] - off[c];
-    std::sort(row, row + cnt, lt);
-    for (uint32_t k = 1; k < cnt; k++)
-      if (row[k].x == row[k - 1].x && row[k].y == row[k - 1].y)
-        return set_err("duplicate decision key (cluster " + std::to_string(c) + ")");
-  }
-  Tables t;
-  t.mode = 1;
-  hipError_t e = upload(&t.tape, tab.data(), n);
-  if (e == hipSuccess) e = upload(&t.doff, off.data(), off.size());
-  return install_staged(b, t, e, "decision table");
+  return stage_slices(b, OWN_REPLAY, rows.data(), C, tab.data(), nullptr, nullptr, nullptr);
 }
 
 int mr_batch_set_decisions(mr_batch* b, const mr_decision* d, size_t n) {
@@ -693,86 +771,27 @@ int mr_batch_set_decisions(mr_batch* b, const mr_decision* d, size_t n) {
 }
 
 // A variant batch (madraft_sim.h mr_batch_set_variant_groups; mr_batch_set_variants is its
-// one-group case, group_of == nullptr = every cluster in group 0): the groups' base tapes one after
-// the other, each slice sorted once, each base record's edit index within its group beside it, the
-// edits' words in group order, one 16-B descriptor per cluster copied from its group, and one mask
-// row per cluster. Validated and staged whole before the previous tables are dropped, like
-// set_decisions_impl.
+// one-group case, group_of == nullptr = every cluster in group 0): what a variant's entry points
+// ask of their ranges, then stage_slices
 static int set_variants_impl(mr_batch* b, const mr_variant_group* groups, size_t n_groups,
                              const mr_decision* base, size_t n, const mr_decision* edits,
                              size_t n_edits, const uint32_t* group_of, const uint32_t* masks) {
-  const size_t C = b->D.C;
   if (n >= (1ull << 32) || n_edits >= (1ull << 32) || n_groups >= (1ull << 32))
     return set_err("too many decisions for one batch (2^32 - 1 at most)");
-  const bool many = group_of != nullptr;  // (messages name the group only where there are groups)
-  auto in_group = [&](size_t g) { return many ? " (group " + std::to_string(g) + ")" : std::string(); };
-  size_t rows = 0, words = 0, widest = 0;
+  const bool many = group_of != nullptr;
   for (size_t g = 0; g < n_groups; g++) {
     const mr_variant_group& G = groups[g];
-    if (G.n_base == 0) return set_err("a variant group needs a base tape, n_base >= 1" + in_group(g));
-    if ((uint64_t)G.base_off + G.n_base > n) return set_err("base range overruns n" + in_group(g));
-    if ((uint64_t)G.edit_off + G.n_edits > n_edits) return set_err("edit range overruns n_edits" + in_group(g));
-    rows += G.n_base;
-    words += G.n_edits;
-    if (G.n_edits > widest) widest = G.n_edits;
+    if (G.n_base == 0) return set_err("a variant group needs a base tape, n_base >= 1" + in_group(many, g));
+    if ((uint64_t)G.base_off + G.n_base > n) return set_err("base range overruns n" + in_group(many, g));
+    if ((uint64_t)G.edit_off + G.n_edits > n_edits)
+      return set_err("edit range overruns n_edits" + in_group(many, g));
   }
-  if (rows >= (1ull << 32) || words >= (1ull << 32))
-    return set_err("too many decisions for one batch (2^32 - 1 at most)");
   if (many)
-    for (size_t c = 0; c < C; c++)
+    for (size_t c = 0; c < b->D.C; c++)
       if (group_of[c] >= n_groups)
         return set_err("group_of[" + std::to_string(c) + "] = " + std::to_string(group_of[c]) +
                        ": no such group");
-  auto key_of = [](const mr_decision& r) { return make_uint2(((uint32_t)r.stream << 16) | r.entity, r.seq); };
-  auto bad_stream = [](const mr_decision& r) { return r.stream < MR_DS_TESTER || r.stream > MR_DS_NET; };
-  auto lt = [](const uint4& a, const uint4& c) { return a.x < c.x || (a.x == c.x && a.y < c.y); };
-  std::vector<uint4> tab(rows), desc(n_groups);
-  std::vector<uint32_t> ved(rows, ~0u);
-  std::vector<uint2> vw(words);
-  size_t r0 = 0, w0 = 0;  // the group's first row of tab / ved, its first edit of vw
-  for (size_t g = 0; g < n_groups; g++) {
-    const mr_variant_group& G = groups[g];
-    uint4* row = tab.data() + r0;
-    for (size_t i = 0; i < G.n_base; i++) {
-      const mr_decision& r = base[G.base_off + i];
-      if (bad_stream(r)) return set_err("bad decision stream" + in_group(g));
-      const uint2 k = key_of(r);
-      row[i] = make_uint4(k.x, k.y, r.w0, r.w1);
-    }
-    std::sort(row, row + G.n_base, lt);
-    for (size_t k = 1; k < G.n_base; k++)
-      if (row[k].x == row[k - 1].x && row[k].y == row[k - 1].y)
-        return set_err("duplicate decision key in the base tape" + in_group(g));
-    for (size_t j = 0; j < G.n_edits; j++) {
-      const mr_decision& r = edits[G.edit_off + j];
-      if (bad_stream(r)) return set_err("bad decision stream (edit " + std::to_string(j) + ")" + in_group(g));
-      const uint2 k = key_of(r);
-      const uint4* it = std::lower_bound(row, row + G.n_base, make_uint4(k.x, k.y, 0, 0), lt);
-      if (it == row + G.n_base || it->x != k.x || it->y != k.y)
-        return set_err("edit " + std::to_string(j) + ": its key is not in the base tape" + in_group(g));
-      uint32_t& e = ved[r0 + (it - row)];
-      if (e != ~0u)
-        return set_err("duplicate edit key (edits " + std::to_string(e) + " and " + std::to_string(j) + ")" +
-                       in_group(g));
-      e = (uint32_t)j;
-      vw[w0 + j] = make_uint2(r.w0, r.w1);
-    }
-    desc[g] = make_uint4((uint32_t)r0, G.n_base, (uint32_t)w0, G.seed_cluster);
-    r0 += G.n_base;
-    w0 += G.n_edits;
-  }
-  std::vector<uint4> cdesc(C);
-  for (size_t c = 0; c < C; c++) cdesc[c] = desc[many ? group_of[c] : 0];
-  const size_t W = (widest + 31) / 32, mw = C * W;
-  Tables t;
-  t.vW = (uint32_t)W;
-  t.mode = 3;
-  hipError_t e = upload(&t.tape, tab.data(), rows);
-  if (e == hipSuccess) e = upload(&t.vdesc, cdesc.data(), C);
-  if (e == hipSuccess) e = upload(&t.vedit, ved.data(), rows);
-  if (e == hipSuccess) e = upload(&t.vwords, vw.data(), words);
-  if (e == hipSuccess) e = upload(&t.vmask, masks, mw);
-  return install_staged(b, t, e, "variant tables");
+  return stage_slices(b, OWN_VARIANTS, groups, n_groups, base, edits, group_of, masks);
 }
 
 // what the two variant calls share before their tables are looked at; 1 = go on
@@ -783,7 +802,7 @@ static int variants_enter(mr_batch* b, bool drop) {
   HIPCHK(hipSetDevice(b->cfg.device));
   HIPCHK(hipStreamSynchronize(b->stream));
   if (!drop) return 1;
-  if (b->D.tape_mode == 3u) drop_decisions(b);  // (another kind of table is not a variant's to drop)
+  if (b->dec.mode == OWN_VARIANTS) drop_decisions(b);  // (another kind of table is not a variant's to drop)
   return 0;
 }
 
@@ -813,7 +832,7 @@ int mr_batch_set_variant_groups(mr_batch* b, const mr_variant_group* groups, siz
 
 int mr_batch_set_variant_masks(mr_batch* b, const uint32_t* masks) {
   if (!b) return set_err("null batch");
-  if (b->D.tape_mode != 3u) return set_err("mr_batch_set_variant_masks without variants");
+  if (b->dec.mode != OWN_VARIANTS) return set_err("mr_batch_set_variant_masks without variants");
   HIPCHK(hipSetDevice(b->cfg.device));
   HIPCHK(hipStreamSynchronize(b->stream));
   const size_t mw = (size_t)b->D.C * b->D.vW;
@@ -831,7 +850,7 @@ static int mr_batch_get_decisions_impl(mr_batch* b, uint32_t k, mr_decision* out
   uint32_t used = 0;
   HIPCHK(hipMemcpy(&used, b->D.cs32 + CS_IDX(CS_TAPE, k, b->D.C), 4, hipMemcpyDeviceToHost));
   *n = used;
-  if (b->D.tape_mode != 2 || !out) return 0;
+  if (b->D.tape_mode != TAPE_RECORD || !out) return 0;
   size_t m = used < b->D.dcap ? used : b->D.dcap;
   if (m > cap) m = cap;
   std::vector<uint4> rows(m);
@@ -856,7 +875,7 @@ static int get_decisions_packed_impl(mr_batch* b, uint32_t first, uint32_t count
   const uint32_t* used_d = b->D.cs32 + CS_IDX(CS_TAPE, first, b->D.C);
   std::vector<uint32_t> used(count);
   if (count) HIPCHK(hipMemcpy(used.data(), used_d, (size_t)count * 4, hipMemcpyDeviceToHost));
-  const bool rec = b->D.tape_mode == 2u;  // (with decisions set the counts are misses: no records)
+  const bool rec = b->D.tape_mode == TAPE_RECORD;  // (with decisions set the counts are misses: no records)
   off[0] = 0;
   for (size_t i = 0; i < count; i++) {
     if (drawn) drawn[i] = used[i];
@@ -967,11 +986,11 @@ int mr_batch_get_decisions_packed(mr_batch* b, uint32_t first, uint32_t count, u
 }
 
 // The batch's seed list: uploaded whole before the previous one is freed; the tables stay, and with
-// them their mode (a list alone: mode 4; dropped without tables: the batch's pool / step kernel again)
+// them what a draw does (a list alone: TAPE_SEEDS; dropped without tables: the batch's pool / step kernel again)
 int mr_batch_set_seeds(mr_batch* b, const uint32_t* seed_cluster) {
   if (!b) return set_err("null batch");
   if (b->submitted) return set_err("batch has a submitted step: mr_batch_finish it first");
-  if (seed_cluster && b->D.tape_mode == 3u)
+  if (seed_cluster && b->dec.mode == OWN_VARIANTS)
     return set_err("a seed list on a batch with variants set");
   HIPCHK(hipSetDevice(b->cfg.device));
   HIPCHK(hipStreamSynchronize(b->stream));

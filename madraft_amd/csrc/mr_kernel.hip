@@ -277,79 +277,64 @@ __device__ __forceinline__ uint2 philox2(uint32_t c0, uint32_t c1, uint32_t c2, 
   }
   return make_uint2(c0, c1);
 }
+// first record of the sorted slice tb[0 .. n) whose key is >= (khi, seq); n if there is none
+DI uint32_t tape_lower_bound(const uint4* tb, uint32_t n, uint32_t khi, uint32_t seq) {
+  uint32_t lo = 0;
+  while (n) {  // (lanes of one group probe the same rows until their keys part: coalesced loads;
+               // slices differ in length, so the trip count is the wave's longest)
+    const uint32_t h = n >> 1;
+    const uint4 r = tb[lo + h];
+    if (r.x < khi || (r.x == khi && r.y < seq)) { lo += h + 1; n -= h + 1; }
+    else n = h;
+  }
+  return lo;
+}
 // the cluster's draw: counter (c0, c1, c2) = (seq, entity, stream), key = its seed
-// (SEMANTICS §2). In MR_TAPE builds with keyed decisions set (§12), replay looks the key up
-// in the cluster's sorted table (a miss takes the Philox draw and is counted), record
-// appends {key, words} in draw order, and a variant batch looks the key up in the slice of the
-// one table that the cluster's group owns, takes an edit's words where the cluster's mask says
-// so, and draws its misses from the group's seed. With a seed list set (§12.3) the cluster's seed
-// is the one the list names for its position, in these builds only.
+// (SEMANTICS §2). In MR_TAPE builds (§12) a draw does one of three things (mr_dev.h TapeMode): it
+// looks its key up in the sorted slice of the one table that the cluster's group owns (replay: the
+// cluster's own row), taking an edit's words where the cluster's mask says so, and a miss is
+// counted and drawn; or it is drawn and appended to the cluster's tape as {key, words}; or it is
+// only drawn. What those builds draw follows one seed rule: the seed the list names for the
+// cluster's position if a list is set (§12.3), else its group's seed_cluster, else its own.
 DI void philox(const Dev& D, X& x, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t& w0,
                uint32_t& w1) {
-  uint32_t sc = x.c;  // the seed's cluster: a variant's is its group's seed_cluster
+  uint32_t sc = x.c;  // the seed's cluster
+  const uint32_t khi = (c2 << 16) | c1;
   if constexpr (MR_TAPE) {
-    if (D.tape_mode) {
-      const uint32_t khi = (c2 << 16) | c1;
-      if (D.tape_mode == 1u) {  // lower bound over the cluster's CSR row (sorted by key)
-        const uint4* tb = D.dtab + D.doff[x.c];
-        uint32_t lo = 0, n = D.doff[x.c + 1] - D.doff[x.c];
-        while (n) {  // first record with key >= (khi, c0)
-          const uint32_t h = n >> 1;
-          const uint4 r = tb[lo + h];
-          if (r.x < khi || (r.x == khi && r.y < c0)) { lo += h + 1; n -= h + 1; }
-          else n = h;
-        }
-        if (lo < D.doff[x.c + 1] - D.doff[x.c]) {
-          const uint4 r = tb[lo];
-          if (r.x == khi && r.y == c0) { w0 = r.z; w1 = r.w; return; }
-        }
-        CS(CS_TAPE) = CS(CS_TAPE) + 1u;  // no record: the seed's own draw
-      } else if (D.tape_mode == 3u) {  // variants (§12.1, §12.2): the cluster's group's sorted slice
-        const uint4 g = D.vdesc[x.c];  // {slice offset, records, first edit, seed_cluster}
-        const uint4* tb = D.dtab + g.x;
-        uint32_t lo = 0, n = g.y;
-        while (n) {  // (lanes of one group probe the same rows until their keys part: coalesced
-                     // loads; slices differ in length, so the trip count is the wave's longest)
-          const uint32_t h = n >> 1;
-          const uint4 r = tb[lo + h];
-          if (r.x < khi || (r.x == khi && r.y < c0)) { lo += h + 1; n -= h + 1; }
-          else n = h;
-        }
-        if (lo < g.y) {
-          const uint4 r = tb[lo];
-          const uint32_t e = D.vedit[g.x + lo];  // the record's edit in its group, ~0u = none (issued with r)
-          if (r.x == khi && r.y == c0) {
-            w0 = r.z; w1 = r.w;
-            if (e != ~0u) {  // the cluster's mask bit and the edit's words, loaded together
-              const uint32_t m = D.vmask[(size_t)x.c * D.vW + (e >> 5)];
-              const uint2 ew = D.vwords[g.z + e];
-              if ((m >> (e & 31u)) & 1u) { w0 = ew.x; w1 = ew.y; }
-            }
-            return;
+    if (D.tape_mode == TAPE_LOOKUP) {
+      const uint4 g = D.tdesc[x.c];  // {slice offset, records, first edit, seed_cluster}
+      const uint4* tb = D.dtab + g.x;
+      const uint32_t lo = tape_lower_bound(tb, g.y, khi, c0);
+      if (lo < g.y) {
+        const uint4 r = tb[lo];
+        uint32_t e = ~0u;  // the record's edit in its group, ~0u = none (issued with r)
+        if (D.vedit) e = D.vedit[g.x + lo];
+        if (r.x == khi && r.y == c0) {
+          w0 = r.z; w1 = r.w;
+          if (e != ~0u) {  // the cluster's mask bit and the edit's words, loaded together
+            const uint32_t m = D.vmask[(size_t)x.c * D.vW + (e >> 5)];
+            const uint2 ew = D.vwords[g.z + e];
+            if ((m >> (e & 31u)) & 1u) { w0 = ew.x; w1 = ew.y; }
           }
+          return;
         }
-        CS(CS_TAPE) = CS(CS_TAPE) + 1u;  // no record: the group's seed, whatever x.c (below)
-        sc = g.w;
-      } else if (D.tape_mode == 2u) {
-        uint4* tb = D.dtab + (size_t)x.c * D.dcap;
-        const uint64_t seed = D.seed0 + (D.sof ? D.sof[x.c] : x.c);  // (a seed list: that seed's tape)
-        const uint2 w = philox2(c0, c1, c2, (uint32_t)seed, (uint32_t)(seed >> 32));
-        w0 = w.x;
-        w1 = w.y;
-        const uint32_t p = CS(CS_TAPE);
-        CS(CS_TAPE) = p + 1u;
-        if (p < D.dcap) tb[p] = make_uint4(khi, c0, w0, w1);
-        return;
       }
-      // a seed list (§12.3; never with variants): a replay's miss, and every draw of a batch with
-      // the list alone (tape_mode 4), takes the draw of the seed the list names for this position
-      if (D.sof) sc = D.sof[x.c];
+      CS(CS_TAPE) = CS(CS_TAPE) + 1u;  // no record: drawn from the group's seed, whatever x.c
+      sc = g.w;
     }
+    if (D.sof) sc = D.sof[x.c];  // (a list and variants exclude each other)
   }
   const uint64_t seed = D.seed0 + sc;
   const uint2 w = philox2(c0, c1, c2, (uint32_t)seed, (uint32_t)(seed >> 32));
   w0 = w.x;
   w1 = w.y;
+  if constexpr (MR_TAPE) {
+    if (D.tape_mode == TAPE_RECORD) {  // (with a seed list: that seed's tape)
+      const uint32_t p = CS(CS_TAPE);
+      CS(CS_TAPE) = p + 1u;
+      if (p < D.dcap) D.dtab[(size_t)x.c * D.dcap + p] = make_uint4(khi, c0, w0, w1);
+    }
+  }
 }
 DI size_t logi(const Dev& D, const X& x, uint32_t d, uint32_t i) {
   return ((size_t)x.c * D.n + GI(d, D.n, G_LOG)) * D.log_cap + (i & (D.log_cap - 1u));
@@ -851,8 +836,8 @@ DI Dev dev_launder(const Dev& D0) {
   D.seed0 = ((uint64_t)glu((uint32_t)(D0.seed0 >> 32)) << 32) | glu((uint32_t)D0.seed0);
   D.M = glu(D0.M); D.K = glu(D0.K); D.hb = glu(D0.hb); D.elo = glu(D0.elo); D.ehi = glu(D0.ehi);
   D.safety = glu(D0.safety); D.max_events = glu(D0.max_events);
-  if constexpr (MR_TAPE) {  // a variant batch's tables (null otherwise)
-    D.vdesc = glp(D0.vdesc); D.vedit = glp(D0.vedit); D.vwords = glp(D0.vwords);
+  if constexpr (MR_TAPE) {  // a lookup's descriptors, a variant batch's edits (null otherwise)
+    D.tdesc = glp(D0.tdesc); D.vedit = glp(D0.vedit); D.vwords = glp(D0.vwords);
     D.vmask = glp(D0.vmask);
     D.sof = glp(D0.sof);  // a seed list (null otherwise)
   }

@@ -213,6 +213,82 @@ def test_replay_many_equals_replay_per_seed(hip):
     assert hip.replay_many(test, [], [], **ckw) == []
 
 
+N_MIX = 70  # one full wave and six lanes
+
+
+@functools.lru_cache(maxsize=None)
+def _mix_recorded():
+    """The oracle's recording of seeds 0 .. N_MIX - 1 stopped after SMALL_EVENTS events: their
+    tapes in draw order and their plain verdicts."""
+    o = vu.oracle()
+    with o.recording(N_MIX, 4096) as (count, rec):
+        code, t, dig, _ = o.run_batch(vu.cfg_of("figure_8", 0, max_events=SMALL_EVENTS), 0, N_MIX)
+    assert 2 <= int(count.min()) and int(count.max()) <= 4096
+    tapes = [rec[k, : int(count[k])].copy() for k in range(N_MIX)]
+    return tapes, [(int(code[k]), int(t[k]), int(dig[k])) for k in range(N_MIX)]
+
+
+def _mix_cut(tape, c):
+    """What position c is given of `tape`, by c % 4: all of it, nothing, every second record, its
+    first record only. (The last position, 69, is an empty one: the table's last row is empty.)"""
+    return (tape, tape[:0], tape[::2], tape[:1])[c % 4]
+
+
+def _mix_load(cut):
+    """The positions' tapes, each naming its position, concatenated in a shuffled order."""
+    order = np.random.default_rng(11).permutation(N_MIX)
+    return np.concatenate([_positional(cut[c], c) for c in order])
+
+
+def _mix_check(b, want, whole_of):
+    """The batch's run equals `want` [(code, time, digest, misses)] at every position; a whole tape
+    misses nothing, an empty one misses every draw of its seed's recorded run and ends as it did."""
+    tapes, plain = _mix_recorded()
+    got = _run(b)
+    drawn, off, rec = b.decisions_all()
+    assert off.tolist() == [0] * (N_MIX + 1) and rec.size == 0
+    for c in range(N_MIX):
+        assert got[c] + (int(drawn[c]),) == want[c], (c, got[c], int(drawn[c]), want[c])
+        assert b.decisions(c)[0] == want[c][3], c
+        k = whole_of(c)
+        if c % 4 == 0:
+            assert int(drawn[c]) == 0 and got[c] == plain[k], (c, k)
+        if c % 4 == 1:
+            assert int(drawn[c]) == tapes[k].size and got[c] == plain[k], (c, k)
+
+
+def test_empty_and_short_rows_beside_long_ones_in_one_wave(hip):
+    """One lookup serves every slice length a wave can hold at once: 70 positions (a full wave and
+    a partial one) whose tapes are whole (47 .. 118 records), empty, halved or one record long, the
+    last row empty, loaded by one set_decisions call in a shuffled order. The oracle's replay
+    expresses an empty row (every draw of that row misses), so every expected value is its own.
+    Then the same shapes under a permuted seed list: position c replays a cut of the tape of the
+    seed the list names, and its misses draw from that seed."""
+    tapes, plain = _mix_recorded()
+    o = vu.oracle()
+    cut = [_mix_cut(tapes[c], c) for c in range(N_MIX)]
+    assert cut[N_MIX - 1].size == 0 and cut[0].size == tapes[0].size and cut[3].size == 1
+    with o.replaying(np.concatenate([_positional(cut[c], c) for c in range(N_MIX)]), N_MIX) as miss:
+        code, t, dig, _ = o.run_batch(vu.cfg_of("figure_8", 0, max_events=SMALL_EVENTS), 0, N_MIX)
+        want = [(int(code[c]), int(t[c]), int(dig[c]), int(miss[c])) for c in range(N_MIX)]
+    perm = [int(k) for k in np.random.default_rng(13).permutation(N_MIX)]
+    assert perm != sorted(perm)
+    cut2 = [_mix_cut(tapes[k], c) for c, k in enumerate(perm)]
+    want2 = []
+    for c, k in enumerate(perm):  # seed k alone, as the oracle's row 0 (tests/variants_util.py)
+        with o.replaying(_positional(cut2[c], 0), 1) as miss:
+            code, t, dig, _ = o.run_batch(vu.cfg_of("figure_8", k, max_events=SMALL_EVENTS), 0, 1)
+            want2.append((int(code[0]), int(t[0]), int(dig[0]), int(miss[0])))
+    with _batch(hip, "figure_8", N_MIX, max_events=SMALL_EVENTS) as b:
+        b.set_decisions(_mix_load(cut))
+        assert b.kernel == "step_kernel_tape"
+        _mix_check(b, want, lambda c: c)
+        b.reset(SEED)
+        b.set_seeds([SEED + k for k in perm])
+        b.set_decisions(_mix_load(cut2))
+        _mix_check(b, want2, lambda c: perm[c])
+
+
 def test_rejected_calls_leave_the_batch_as_it_was(hip):
     base = vu.recorded("figure_8", 0)[0]
     idx, edits = shrink.find_edits(base, "drop")
