@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -117,56 +118,88 @@ constexpr uint32_t STEP_LANES = 64;  // lanes per step-kernel block (one wave)
 // variant's, a seed list and variants exclude each other, set_variant_masks needs a variant's)
 enum Owner : uint32_t { OWN_NONE, OWN_REPLAY, OWN_RECORD, OWN_VARIANTS };
 
+// Move-only owners of the HIP handles a batch keeps, one per kind: released with their holder
+template <auto Release>
+struct Releaser {
+  template <class P> void operator()(P p) const { (void)Release(p); }
+};
+template <class T> using DevMem = std::unique_ptr<T[], Releaser<hipFree>>;      // device memory
+template <class T> using PinMem = std::unique_ptr<T[], Releaser<hipHostFree>>;  // pinned host memory
+using Stream = std::unique_ptr<ihipStream_t, Releaser<hipStreamDestroy>>;
+using Event = std::unique_ptr<ihipEvent_t, Releaser<hipEventDestroy>>;
+
+// own = the handle `make(&raw)` creates (null where that fails)
+template <class Own, class Make>
+hipError_t acquire(Own& own, Make make) {
+  typename Own::pointer p = nullptr;
+  const hipError_t e = make(&p);
+  own.reset(p);
+  return e;
+}
+// m = a new device array of `count` elements
+template <class T>
+hipError_t dev_alloc(DevMem<T>& m, size_t count) {
+  return acquire(m, [&](T** p) { return hipMalloc(p, count * sizeof(T)); });
+}
+
+// dst = a new device array of max(count, 1) elements: src[0 .. count), or zeros for a null src
+template <class T>
+hipError_t upload(DevMem<T>& dst, const T* src, size_t count) {
+  const hipError_t e = dev_alloc(dst, count ? count : 1);
+  if (e != hipSuccess || !count) return e;
+  return src ? hipMemcpy(dst.get(), src, count * sizeof(T), hipMemcpyHostToDevice)
+             : hipMemset(dst.get(), 0, count * sizeof(T));
+}
+
 // A batch's decision tables on the device, each its own allocation, whoever made them: the record
 // tape (MR_F_RECORD), or what stage_slices built, the sorted slices and the clusters' descriptors
 // of a replay, and with them a variant batch's edits and masks. All null: Philox draws.
 struct Tables {
-  uint4* tape = nullptr;      // keyed decisions: the record tape, or the groups' sorted slices
-  uint4* tdesc = nullptr;     // slices: the clusters' group descriptors;
-  uint32_t* vedit = nullptr;  // variants: the base records' edit indices within their group,
-  uint2* vwords = nullptr;    // the edits' words,
-  uint32_t* vmask = nullptr;  // and the clusters' mask rows (set_variant_masks rewrites them)
+  DevMem<uint4> tape;         // keyed decisions: the record tape, or the groups' sorted slices
+  DevMem<uint4> tdesc;        // slices: the clusters' group descriptors;
+  DevMem<uint32_t> vedit;     // variants: the base records' edit indices within their group,
+  DevMem<uint2> vwords;       // the edits' words,
+  DevMem<uint32_t> vmask;     // and the clusters' mask rows (set_variant_masks rewrites them)
   uint32_t dcap = 0, vW = 0;  // Dev's dcap and vW with these tables
   Owner mode = OWN_NONE;
 };
 
-void free_tables(Tables& t) {
-  for (void* p : {(void*)t.tape, (void*)t.tdesc, (void*)t.vedit, (void*)t.vwords, (void*)t.vmask})
-    if (p) (void)hipFree(p);
-  t = Tables{};
-}
+// the HBM format of a run's message keys: the pool kernel's (32-bit, AppendEntries bit), or the one
+// the step and tape kernels share
+enum KeyFormat : uint32_t { KEYS_UNSET, KEYS_POOL, KEYS_STEP };
 
-// *dst = a new device array of max(count, 1) elements: src[0 .. count), or zeros for a null src
-template <class T>
-hipError_t upload(T** dst, const T* src, size_t count) {
-  const hipError_t e = hipMalloc(dst, (count ? count : 1) * sizeof(T));
-  if (e != hipSuccess || !count) return e;
-  return src ? hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice)
-             : hipMemset(*dst, 0, count * sizeof(T));
-}
+// Where a batch's run stands: a reset starts it over, enqueue_step and the launch loop (advance)
+// move it on
+struct RunState {
+  uint32_t c_open = 0;         // first cluster of the first chunk not yet finished
+  bool resume = false;         // streaming: the next launch continues the current chunk
+  KeyFormat keys = KEYS_UNSET; // of the launches since the reset
+  bool submitted = false;      // mr_batch_submit enqueued a step not yet waited for
+  std::chrono::steady_clock::time_point t_submit;
+};
 }  // namespace
 
 struct mr_batch {
+  Stream stream;  // (first: released last, after the events and the memory its work used)
+  Event ev0, ev1;
   mr_cfg cfg;
-  Dev D;
-  void* base = nullptr;
+  Dev D;  // the kernels' view: raw pointers into what the owners below hold
+  DevMem<char> base;
   DevLayout lay;  // where `base` holds D's arrays, and what a reset zeroes
-  unsigned long long* red = nullptr;
-  uint32_t* h_remaining = nullptr;  // [2]: remaining, next unclaimed cluster (D.remaining)
-  uint32_t* h_ctl0 = nullptr;       // [2]: {0, L}, copied to D.remaining before each launch
-  uint32_t c_open = 0;              // first cluster of the first chunk not yet finished
-  uint32_t* held[2] = {nullptr, nullptr};  // streaming: clusters held at a launch's end (ping-pong)
-  uint32_t hsel = 0;                // held[hsel] = the next launch's held_in
-  bool resume = false;              // streaming: the next launch continues the current chunk
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  uint32_t budget = 16384;  // events per cluster per launch (MR_STEP_BUDGET)
-  Tables dec;                // the decision tables D draws from (install_tables)
-  uint32_t* sof = nullptr;   // the seed list (mr_batch_set_seeds): the batch's, not its tables'
-  bool submitted = false;    // mr_batch_submit enqueued a step not yet finished
-  uint32_t kern = 0;         // kernel family of the launches since the reset: 1 pool, 2 step / tape
-  std::chrono::steady_clock::time_point t_submit;
+  DevMem<unsigned long long> red;
+  PinMem<uint32_t> h_remaining;  // [2]: remaining, next unclaimed cluster (D.remaining)
+  PinMem<uint32_t> h_ctl0;       // [2]: {0, L}, copied to D.remaining before each launch
+  DevMem<uint32_t> held[2];      // streaming: clusters held at a launch's end (ping-pong)
+  uint32_t hsel = 0;             // held[hsel] = the next launch's held_in
+  uint32_t budget = 16384;       // events per cluster per launch (MR_STEP_BUDGET)
+  Tables dec;                    // the decision tables D draws from (install_tables)
+  DevMem<uint32_t> sof;          // the seed list (mr_batch_set_seeds): the batch's, not its tables'
+  RunState run;
 };
+struct BatchDestroy {
+  void operator()(mr_batch* b) const { mr_batch_destroy(b); }
+};
+using Batch = std::unique_ptr<mr_batch, BatchDestroy>;
 
 // traced cluster k's row of `rows` ([trace_clusters][trace_cap]): its records so far, at most cap
 template <class T>
@@ -187,13 +220,14 @@ static TapeMode tape_mode_of(const mr_batch* b) {
 }
 
 // `t` (staged whole by the caller) becomes the batch's decision tables, the previous ones are
-// freed, and the kernels' view of them is published into D
-static void install_tables(mr_batch* b, const Tables& t) {
-  free_tables(b->dec);
-  b->dec = t;
+// freed by the move, and the kernels' view of them is published into D
+static void install_tables(mr_batch* b, Tables&& t) {
+  b->dec = std::move(t);
+  const Tables& d = b->dec;
   Dev& D = b->D;
-  D.dtab = t.tape; D.dcap = t.dcap;
-  D.tdesc = t.tdesc; D.vedit = t.vedit; D.vwords = t.vwords; D.vmask = t.vmask; D.vW = t.vW;
+  D.dtab = d.tape.get(); D.dcap = d.dcap;
+  D.tdesc = d.tdesc.get(); D.vedit = d.vedit.get(); D.vwords = d.vwords.get();
+  D.vmask = d.vmask.get(); D.vW = d.vW;
   D.tape_mode = tape_mode_of(b);
 }
 
@@ -265,14 +299,19 @@ static int mr_batch_create_impl(const mr_cfg* cfg, mr_batch** out) {
   *out = nullptr;
   if (validate(cfg) != 0) return -1;
   const uint32_t scn = cfg->scenario;
+  const uint64_t C = cfg->n_clusters, n = cfg->n_nodes, M = cfg->msg_slots;
+  // field matrices use 32-bit element offsets in the kernels
+  const uint64_t lim = 1ull << 32;
+  if ((uint64_t)CS_STRIDE * C >= lim || (uint64_t)C64_STRIDE * C >= lim || M * C >= lim)
+    return set_err("n_clusters too large for one batch (32-bit field offsets)");
 
-  mr_batch* b = new mr_batch();
+  Batch b(new mr_batch());  // (every exit below releases what the batch holds by then)
   b->cfg = *cfg;
   Dev& D = b->D;
   std::memset(&D, 0, sizeof D);
-  const uint64_t C = cfg->n_clusters, n = cfg->n_nodes, M = cfg->msg_slots;
+  const uint64_t per_chunk = cfg->lanes && cfg->lanes < C ? cfg->lanes : C;  // clusters, as configured
   D.C = (uint32_t)C;
-  D.L = cfg->lanes && cfg->lanes < C ? cfg->lanes : (uint32_t)C;  // no tape: capacity (below)
+  D.L = (uint32_t)per_chunk;  // no tape: capacity (below)
   D.stream = (cfg->flags & MR_F_STREAM) ? 1u : 0u;
   D.n = (uint32_t)n; D.log_cap = cfg->log_cap; D.apply_cap = cfg->apply_cap;
   D.M = (uint32_t)M; D.K = cfg->ae_max; D.hb = cfg->hb_us; D.elo = cfg->elect_lo_us;
@@ -292,132 +331,111 @@ static int mr_batch_create_impl(const mr_cfg* cfg, mr_batch** out) {
   D.seed0 = cfg->seed_base + cfg->cluster_base;
   D.pool = !(cfg->flags & MR_F_RECORD) && use_pool(scn, (uint32_t)n, (uint32_t)M) ? 1u : 0u;
 
-  // field matrices use 32-bit element offsets in the kernels
-  const uint64_t lim = 1ull << 32;
-  if ((uint64_t)CS_STRIDE * C >= lim || (uint64_t)C64_STRIDE * C >= lim || M * C >= lim) {
-    delete b;
-    return set_err("n_clusters too large for one batch (32-bit field offsets)");
-  }
   b->lay = dev_layout(*cfg);  // one allocation; every array 256-B aligned (mr_dev.h MR_DEV_ARRAYS)
   hipError_t e = hipSetDevice(cfg->device);
-  if (e == hipSuccess) e = hipMalloc(&b->base, b->lay.off[A__N]);
-  if (e == hipSuccess) e = hipMalloc(&b->red, RED_N * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipHostMalloc(&b->h_remaining, 2 * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipHostMalloc(&b->h_ctl0, 2 * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreate(&b->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&b->ev1);
-  if (e != hipSuccess) {
-    std::string msg = std::string("allocation of ") + std::to_string(b->lay.off[A__N]) + " B failed: " +
-                      hipGetErrorString(e);
-    mr_batch_destroy(b);
-    return set_err(msg);
-  }
-  dev_carve(D, b->lay, static_cast<char*>(b->base));
+  if (e == hipSuccess) e = dev_alloc(b->base, b->lay.off[A__N]);
+  if (e == hipSuccess) e = dev_alloc(b->red, RED_N);
+  const auto pinned2 = [](uint32_t** p) { return hipHostMalloc(p, 2 * sizeof(uint32_t)); };
+  const auto stream = [](hipStream_t* p) { return hipStreamCreateWithFlags(p, hipStreamNonBlocking); };
+  if (e == hipSuccess) e = acquire(b->h_remaining, pinned2);
+  if (e == hipSuccess) e = acquire(b->h_ctl0, pinned2);
+  if (e == hipSuccess) e = acquire(b->stream, stream);
+  if (e == hipSuccess) e = acquire(b->ev0, hipEventCreate);
+  if (e == hipSuccess) e = acquire(b->ev1, hipEventCreate);
+  if (e != hipSuccess)
+    return set_err(std::string("allocation of ") + std::to_string(b->lay.off[A__N]) + " B failed: " +
+                   hipGetErrorString(e));
+  dev_carve(D, b->lay, b->base.get());
   if (cfg->flags & MR_F_RECORD) {
     Tables t;  // (the tape is written before it is read: not filled)
-    e = hipMalloc(&t.tape, (size_t)C * cfg->tape_cap * sizeof(uint4));
-    if (e != hipSuccess) {
-      mr_batch_destroy(b);
-      return set_err(std::string("tape allocation failed: ") + hipGetErrorString(e));
-    }
+    e = dev_alloc(t.tape, (size_t)C * cfg->tape_cap);
+    if (e != hipSuccess) return set_err(std::string("tape allocation failed: ") + hipGetErrorString(e));
     t.dcap = cfg->tape_cap;
     t.mode = OWN_RECORD;
-    install_tables(b, t);
+    install_tables(b.get(), std::move(t));
   }
-  if (hipMemset(b->D.prof, 0, PROF_SLOTS * sizeof(unsigned long long)) != hipSuccess ||
-      hipMemset(b->D.guard, 0, 4 * sizeof(uint32_t)) != hipSuccess) {
-    mr_batch_destroy(b);
+  if (hipMemset(D.prof, 0, PROF_SLOTS * sizeof(unsigned long long)) != hipSuccess ||
+      hipMemset(D.guard, 0, 4 * sizeof(uint32_t)) != hipSuccess)
     return set_err("hipMemset failed");
-  }
   // lanes per wave: as configured, else 32 when the batch (or its chunk) fills at most half of
   // the resident lanes — two half-full waves per SIMD hide the latency chains better than one
   // full one — else 64
-  const uint32_t cap = step_capacity(b->D, scn, cfg->device);  // resident lanes (64 per wave)
-  b->D.lpw = cfg->lanes_per_wave ? cfg->lanes_per_wave
-             : (cap && (uint64_t)(cfg->lanes && cfg->lanes < C ? cfg->lanes : C) * 2u <= cap) ? 32u : 64u;
+  const uint32_t cap = step_capacity(D, scn, cfg->device);  // resident lanes (64 per wave)
+  D.lpw = cfg->lanes_per_wave ? cfg->lanes_per_wave : (cap && per_chunk * 2u <= cap) ? 32u : 64u;
   if (!cfg->lanes) {  // a batch bigger than the resident waves runs as chunks of that size
-    const uint32_t capc = (uint32_t)((uint64_t)cap * b->D.lpw / STEP_LANES);
-    if (capc && capc < b->D.C) {
-      b->D.L = capc;
+    const uint32_t capc = (uint32_t)((uint64_t)cap * D.lpw / STEP_LANES);
+    if (capc && capc < D.C) {
+      D.L = capc;
       // a pool kernel refills its slots from the rest of the batch (streaming) instead of
       // draining once per chunk (config 3's whole job on one GPU +10 %)
-      if (b->D.pool && !b->D.tape_mode) b->D.stream = 1u;
+      if (family_of(D) == F_POOL) D.stream = 1u;
     }
   }
-  if (b->D.stream) {  // held-cluster lists, L entries each (L <= C)
-    e = hipMalloc(&b->held[0], (size_t)b->D.C * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&b->held[1], (size_t)b->D.C * sizeof(uint32_t));
-    if (e != hipSuccess) {
-      mr_batch_destroy(b);
-      return set_err(std::string("held-list allocation failed: ") + hipGetErrorString(e));
-    }
+  if (D.stream) {  // held-cluster lists, L entries each (L <= C)
+    e = dev_alloc(b->held[0], D.C);
+    if (e == hipSuccess) e = dev_alloc(b->held[1], D.C);
+    if (e != hipSuccess) return set_err(std::string("held-list allocation failed: ") + hipGetErrorString(e));
   }
   // the 7-server Raft pool's LDS key rows (32); MR_KEY_ROWS (tests) puts more slots' keys in HBM
-  b->D.krows = 32u;
+  D.krows = 32u;
   if (const char* s = std::getenv("MR_KEY_ROWS")) {
     const int r = std::atoi(s);
-    if (r >= 1 && r <= 32) b->D.krows = (uint32_t)r;
+    if (r >= 1 && r <= 32) D.krows = (uint32_t)r;
   }
   if (const char* s = std::getenv("MR_STEP_BUDGET")) b->budget = (uint32_t)std::atoi(s);
   if (b->budget == 0) b->budget = 16384;
-  if (mr_batch_reset(b, cfg->seed_base) != 0) {
-    std::string msg = g_err;
-    mr_batch_destroy(b);
-    return set_err(msg);
-  }
-  *out = b;
+  if (mr_batch_reset(b.get(), cfg->seed_base) != 0) return -1;  // (its message stands: a destroy sets none)
+  *out = b.release();
   return 0;
 }
 
 static int enqueue_reset(mr_batch* b, uint64_t seed_base) {
   b->cfg.seed_base = seed_base;
-  b->kern = 0;
-  b->c_open = 0;
-  b->resume = false;
+  b->run = RunState{};
   b->D.seed0 = seed_base + b->cfg.cluster_base;
   HIPCHK(hipSetDevice(b->cfg.device));
   for (int k = 0; k < (int)A__N; k++)  // the table's ZERO rows this batch has, by their place k
     for (uint32_t a = 0; a < A__N; a++)
       if (k_dev_reset[a] == k && b->lay.bytes[a])
-        HIPCHK(hipMemsetAsync(static_cast<char*>(b->base) + b->lay.off[a], 0, b->lay.bytes[a], b->stream));
+        HIPCHK(hipMemsetAsync(b->base.get() + b->lay.off[a], 0, b->lay.bytes[a], b->stream.get()));
 #if MR_GUARD
   b->D.gprobe = std::getenv("MR_GUARD_PROBE") ? 1u : 0u;
 #endif
-  HIPCHK(launch_reset(b->D, b->stream));
+  HIPCHK(launch_reset(b->D, b->stream.get()));
   return 0;
 }
 
-// one step-kernel launch on the batch stream, bracketed by the timing events;
-// the remaining-cluster count is copied back asynchronously
-static int enqueue_step(mr_batch* b, uint32_t budget) {
-  // the pool kernel's message keys (32-bit, AppendEntries bit) and the step / tape kernels' are
-  // different HBM formats: a run does not switch family between its launches
-  const uint32_t kern = b->D.pool && !b->D.tape_mode ? 1u : 2u;
-  if (b->kern && b->kern != kern)
+// one step-kernel launch on the batch stream for the chunk that starts at cluster c0, bracketed by
+// the timing events; the remaining-cluster count is copied back asynchronously
+static int enqueue_step(mr_batch* b, uint32_t c0, uint32_t budget) {
+  RunState& r = b->run;
+  Dev& D = b->D;
+  // a run does not switch key format between its launches
+  const KeyFormat keys = family_of(D) == F_POOL ? KEYS_POOL : KEYS_STEP;
+  if (r.keys != KEYS_UNSET && r.keys != keys)
     return set_err("decisions set or dropped in the middle of a pool-kernel run: mr_batch_reset first");
-  b->kern = kern;
+  r.keys = keys;
+  D.c0 = c0;
   b->h_ctl0[0] = 0;
-  if (b->D.stream && b->resume) {  // continue: the held clusters first, the claim pointer kept
+  if (D.stream && r.resume) {  // continue: the held clusters first, the claim pointer kept
     b->h_ctl0[1] = b->h_remaining[1];
-    b->D.nheld = b->h_remaining[0];
-    b->D.resume = 1;
+    D.nheld = b->h_remaining[0];
+    D.resume = 1;
   } else {
-    b->h_ctl0[1] = b->D.c0 + b->D.L;  // lanes start with clusters c0 .. c0+L-1 (streaming: claim on)
-    b->D.nheld = 0;
-    b->D.resume = 0;
+    b->h_ctl0[1] = c0 + D.L;  // lanes start with clusters c0 .. c0+L-1 (streaming: claim on)
+    D.nheld = 0;
+    D.resume = 0;
   }
-  b->D.held_in = b->held[b->hsel];
-  b->D.held_out = b->held[b->hsel ^ 1u];
+  D.held_in = b->held[b->hsel].get();
+  D.held_out = b->held[b->hsel ^ 1u].get();
   b->hsel ^= 1u;
-  b->resume = b->D.stream != 0;
-  HIPCHK(hipMemcpyAsync(b->D.remaining, b->h_ctl0, 2 * sizeof(uint32_t), hipMemcpyHostToDevice,
-                        b->stream));
-  HIPCHK(hipEventRecord(b->ev0, b->stream));
-  HIPCHK(launch_step(b->D, b->D.scenario, budget, b->stream));
-  HIPCHK(hipEventRecord(b->ev1, b->stream));
-  HIPCHK(hipMemcpyAsync(b->h_remaining, b->D.remaining, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                        b->stream));
+  r.resume = D.stream != 0;
+  hipStream_t stream = b->stream.get();
+  HIPCHK(hipMemcpyAsync(D.remaining, b->h_ctl0.get(), 2 * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipEventRecord(b->ev0.get(), stream));
+  HIPCHK(launch_step(D, D.scenario, budget, stream));
+  HIPCHK(hipEventRecord(b->ev1.get(), stream));
+  HIPCHK(hipMemcpyAsync(b->h_remaining.get(), D.remaining, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   return 0;
 }
 
@@ -444,56 +462,64 @@ static int guard_check(mr_batch* b) {
 
 int mr_batch_reset(mr_batch* b, uint64_t seed_base) {
   if (!b) return set_err("null batch");
-  if (b->submitted) return set_err("batch has a submitted step: mr_batch_finish it first");
+  if (b->run.submitted) return set_err("batch has a submitted step: mr_batch_finish it first");
   if (enqueue_reset(b, seed_base) != 0) return -1;
-  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream.get()));
+  return 0;
+}
+
+// The one launch loop. Chunks of D.L clusters, one after another (a streaming batch is one chunk of
+// all clusters), each by launches of at most the budget's events per cluster: enqueue a step (a
+// submitted batch has its first one in flight), wait, account it, close the chunk when nothing of
+// it remains. A call cut short by max_events (0: no bound) resumes with the chunk it stopped in.
+static int advance(mr_batch* b, uint64_t max_events, mr_run_stats& s) {
+  RunState& r = b->run;
+  const uint32_t chunk = b->D.stream ? b->D.C : b->D.L;
+  for (uint64_t done_events = 0; r.c_open < b->D.C;) {
+    uint32_t budget = b->budget;
+    if (!r.submitted) {
+      if (max_events) {
+        if (done_events >= max_events) break;
+        budget = (uint32_t)std::min<uint64_t>(budget, max_events - done_events);
+      }
+      if (enqueue_step(b, r.c_open, budget) != 0) return -1;
+    }
+    HIPCHK(hipStreamSynchronize(b->stream.get()));
+    r.submitted = false;
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, b->ev0.get(), b->ev1.get()));
+    s.kernel_ms += ms;
+    s.launches++;
+    done_events += budget;
+    if (remaining_after(b) == 0) r.c_open += chunk;
+  }
+  return 0;
+}
+
+// mr_batch_run and mr_batch_finish: the loop, then once per call the guard's verdict and the counter
+// reduce (events processed and clusters left are sums over the per-cluster counters)
+static int run_from(mr_batch* b, uint64_t max_events, std::chrono::steady_clock::time_point t0,
+                    mr_run_stats* st, mr_counters* cnt) {
+  HIPCHK(hipSetDevice(b->cfg.device));
+  mr_run_stats s;
+  std::memset(&s, 0, sizeof s);
+  const int rc = advance(b, max_events, s);
+  b->D.c0 = 0;  // (a launch's argument: 0 between calls, whichever way the loop ended)
+  if (rc != 0 || guard_check(b) != 0) return -1;
+  mr_counters c;
+  if (mr_batch_counters(b, &c) != 0) return -1;
+  s.events = c.events;
+  s.remaining = c.clusters - c.done;
+  s.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (st) *st = s;
+  if (cnt) *cnt = c;
   return 0;
 }
 
 int mr_batch_run(mr_batch* b, uint64_t max_events_per_call, mr_run_stats* st) {
   if (!b) return set_err("null batch");
-  if (b->submitted) return set_err("batch has a submitted step: mr_batch_finish it first");
-  HIPCHK(hipSetDevice(b->cfg.device));
-  auto t0 = std::chrono::steady_clock::now();
-  mr_run_stats s;
-  std::memset(&s, 0, sizeof s);
-  uint64_t done_events = 0;
-  bool stop = false;
-  // chunks of D.L clusters, one after another (a streaming batch is one chunk of all clusters);
-  // a call cut short by max_events_per_call resumes with the chunk it stopped in
-  const uint32_t chunk = b->D.stream ? b->D.C : b->D.L;
-  for (uint32_t c0 = b->c_open; c0 < b->D.C && !stop; c0 += chunk) {
-    b->D.c0 = c0;
-    for (;;) {
-      uint32_t budget = b->budget;
-      if (max_events_per_call) {
-        if (done_events >= max_events_per_call) { stop = true; break; }
-        uint64_t left = max_events_per_call - done_events;
-        if (left < budget) budget = (uint32_t)left;
-      }
-      if (enqueue_step(b, budget) != 0) { b->D.c0 = 0; return -1; }
-      HIPCHK(hipStreamSynchronize(b->stream));
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-      s.kernel_ms += ms;
-      s.launches++;
-      done_events += budget;
-      if (remaining_after(b) == 0) {
-        b->c_open = c0 + chunk;
-        break;
-      }
-    }
-  }
-  b->D.c0 = 0;
-  if (guard_check(b) != 0) return -1;
-  s.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  // events processed and clusters left: sums over the per-cluster counters (cheap reduce)
-  mr_counters c;
-  if (mr_batch_counters(b, &c) != 0) return -1;
-  s.events = c.events;
-  s.remaining = c.clusters - c.done;
-  if (st) *st = s;
-  return 0;
+  if (b->run.submitted) return set_err("batch has a submitted step: mr_batch_finish it first");
+  return run_from(b, max_events_per_call, std::chrono::steady_clock::now(), st, nullptr);
 }
 
 // Pipelined steps (bench.py): reset + the first step-kernel launch are only
@@ -501,45 +527,20 @@ int mr_batch_run(mr_batch* b, uint64_t max_events_per_call, mr_run_stats* st) {
 // that batch's waves take the CUs this batch's early-finishing waves free.
 int mr_batch_submit(mr_batch* b, uint64_t seed_base) {
   if (!b) return set_err("null batch");
-  if (b->submitted) return set_err("batch already has a submitted step");
-  b->t_submit = std::chrono::steady_clock::now();
+  if (b->run.submitted) return set_err("batch already has a submitted step");
+  const auto t0 = std::chrono::steady_clock::now();
   if (enqueue_reset(b, seed_base) != 0) return -1;
-  if (enqueue_step(b, b->budget) != 0) return -1;
-  b->submitted = true;
+  if (enqueue_step(b, 0, b->budget) != 0) return -1;
+  b->run.submitted = true;
+  b->run.t_submit = t0;
   return 0;
 }
 
+// the loop from the submitted launch on: clusters past its budget, and later chunks, run here
 int mr_batch_finish(mr_batch* b, mr_run_stats* st, mr_counters* cnt) {
   if (!b) return set_err("null batch");
-  if (!b->submitted) return set_err("no submitted step");
-  HIPCHK(hipSetDevice(b->cfg.device));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  b->submitted = false;
-  mr_run_stats s;
-  std::memset(&s, 0, sizeof s);
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-  s.kernel_ms = ms;
-  s.launches = 1;
-  s.remaining = remaining_after(b);
-  if (s.remaining == 0) b->c_open = b->D.stream ? b->D.C : b->D.L;  // the submitted chunk is done
-  if (b->c_open < b->D.C) s.remaining = 1;  // later chunks: run them below
-  if (s.remaining != 0) {  // clusters past the per-launch budget: finish them synchronously
-    mr_run_stats more;
-    if (mr_batch_run(b, 0, &more) != 0) return -1;
-    s.kernel_ms += more.kernel_ms;
-    s.launches += more.launches;
-    s.remaining = more.remaining;
-  }
-  if (guard_check(b) != 0) return -1;  // (mr_batch_run above checked its own launches)
-  mr_counters c;
-  if (mr_batch_counters(b, &c) != 0) return -1;
-  s.events = c.events;
-  s.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() -
-                                                        b->t_submit).count();
-  if (st) *st = s;
-  if (cnt) *cnt = c;
-  return 0;
+  if (!b->run.submitted) return set_err("no submitted step");
+  return run_from(b, 0, b->run.t_submit, st, cnt);
 }
 
 static int mr_batch_verdicts_impl(mr_batch* b, uint16_t* code, uint32_t* time_us, uint64_t* digest) {
@@ -551,7 +552,7 @@ static int mr_batch_verdicts_impl(mr_batch* b, uint16_t* code, uint32_t* time_us
   auto row = [&](void* dst, const void* base, size_t f, size_t width, bool wide) -> hipError_t {
     const char* p = static_cast<const char*>(base) + (wide ? C64_IDX(f, 0, C) : CS_IDX(f, 0, C)) * width;
     const size_t pitch = (wide ? C64_IDX(f, 1, C) - C64_IDX(f, 0, C) : CS_IDX(f, 1, C) - CS_IDX(f, 0, C)) * width;
-    return hipMemcpy2DAsync(dst, width, p, pitch, width, C, hipMemcpyDeviceToHost, b->stream);
+    return hipMemcpy2DAsync(dst, width, p, pitch, width, C, hipMemcpyDeviceToHost, b->stream.get());
   };
   if (code) {
     c32.resize(C);
@@ -559,7 +560,7 @@ static int mr_batch_verdicts_impl(mr_batch* b, uint16_t* code, uint32_t* time_us
   }
   if (time_us) HIPCHK(row(time_us, b->D.cs32, CS_VTIME, 4, false));
   if (digest) HIPCHK(row(digest, b->D.cs64, C64_DIGEST, 8, true));
-  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream.get()));
   for (size_t i = 0; i < c32.size(); i++) code[i] = (uint16_t)c32[i];
   return 0;
 }
@@ -569,10 +570,10 @@ int mr_batch_counters(mr_batch* b, mr_counters* out) {
   HIPCHK(hipSetDevice(b->cfg.device));
   std::vector<unsigned long long> h(RED_N, 0);
   h[RED_FIRST_FAIL] = ~0ull;
-  HIPCHK(hipMemcpyAsync(b->red, h.data(), RED_N * 8, hipMemcpyHostToDevice, b->stream));
-  HIPCHK(launch_reduce(b->D, b->red, b->cfg.cluster_base, b->stream));
-  HIPCHK(hipMemcpyAsync(h.data(), b->red, RED_N * 8, hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpyAsync(b->red.get(), h.data(), RED_N * 8, hipMemcpyHostToDevice, b->stream.get()));
+  HIPCHK(launch_reduce(b->D, b->red.get(), b->cfg.cluster_base, b->stream.get()));
+  HIPCHK(hipMemcpyAsync(h.data(), b->red.get(), RED_N * 8, hipMemcpyDeviceToHost, b->stream.get()));
+  HIPCHK(hipStreamSynchronize(b->stream.get()));
   std::memset(out, 0, sizeof *out);
   out->clusters = b->D.C;
 #define MR_ROW_(sym, field, red, who) out->field = h[CNT_##sym];
@@ -599,26 +600,28 @@ int mr_batch_counters(mr_batch* b, mr_counters* out) {
   return 0;
 }
 
-int mr_trace_get(mr_batch* b, uint32_t k, mr_event* out, size_t cap, size_t* n) {
+// what the trace getters ask before they copy: a traced cluster, and the batch's stream at rest
+// (it is non-blocking, so the null stream's copies are not ordered after it)
+static int trace_enter(mr_batch* b, uint32_t k, const void* out, const size_t* n) {
   if (!b || !out || !n) return set_err("null argument");
   if (k >= b->D.trace_clusters) return set_err("cluster not traced");
   HIPCHK(hipSetDevice(b->cfg.device));
+  HIPCHK(hipStreamSynchronize(b->stream.get()));
+  return 0;
+}
+
+int mr_trace_get(mr_batch* b, uint32_t k, mr_event* out, size_t cap, size_t* n) {
+  if (trace_enter(b, k, out, n) != 0) return -1;
   return copy_trace_row(b, k, b->D.trace, out, cap, n);
 }
 
 int mr_trace_digests(mr_batch* b, uint32_t k, uint64_t* out, size_t cap, size_t* n) {
-  if (!b || !out || !n) return set_err("null argument");
-  if (k >= b->D.trace_clusters) return set_err("cluster not traced");
-  HIPCHK(hipSetDevice(b->cfg.device));
-  HIPCHK(hipStreamSynchronize(b->stream));
+  if (trace_enter(b, k, out, n) != 0) return -1;
   return copy_trace_row(b, k, b->D.tdig, out, cap, n);
 }
 
 int mr_trace_applies(mr_batch* b, uint32_t k, uint64_t* out, size_t cap, size_t* n) {
-  if (!b || !out || !n) return set_err("null argument");
-  if (k >= b->D.trace_clusters) return set_err("cluster not traced");
-  HIPCHK(hipSetDevice(b->cfg.device));
-  HIPCHK(hipStreamSynchronize(b->stream));
+  if (trace_enter(b, k, out, n) != 0) return -1;
   size_t m = cap < b->D.trace_cap ? cap : b->D.trace_cap;
   HIPCHK(hipMemcpy(out, b->D.tapp + (size_t)k * b->D.trace_cap * 2u, m * 2u * sizeof(uint64_t),
                    hipMemcpyDeviceToHost));
@@ -629,7 +632,11 @@ int mr_trace_applies(mr_batch* b, uint32_t k, uint64_t* out, size_t cap, size_t*
 
 const char* mr_batch_kernel(const mr_batch* b) {
   if (!b) return "";
-  return b->D.tape_mode ? "step_kernel_tape" : b->D.pool ? "pool_kernel" : "step_kernel";
+  switch (family_of(b->D)) {
+    case F_TAPE: return "step_kernel_tape";
+    case F_POOL: return "pool_kernel";
+    default: return "step_kernel";
+  }
 }
 
 uint32_t mr_decision_word(uint32_t v, uint32_t lo, uint32_t hi) {
@@ -641,17 +648,6 @@ uint32_t mr_decision_word(uint32_t v, uint32_t lo, uint32_t hi) {
 
 // the batch's decision tables (whoever installed them) freed; Philox draws
 static void drop_decisions(mr_batch* b) { install_tables(b, Tables{}); }
-
-// `t`, staged by a chain of upload()s that ended with `e`: installed, or on an error freed, the
-// batch keeping its previous tables (`what` names them in the message)
-static int install_staged(mr_batch* b, Tables& t, hipError_t e, const char* what) {
-  if (e != hipSuccess) {
-    free_tables(t);
-    return set_err(std::string(what) + ": " + hipGetErrorString(e));
-  }
-  install_tables(b, t);
-  return 0;
-}
 
 // (a variant batch's messages name the group only where there are groups)
 static std::string in_group(bool many, size_t g) {
@@ -725,14 +721,17 @@ static int stage_slices(mr_batch* b, Owner who, const mr_variant_group* groups, 
   Tables t;
   t.vW = (uint32_t)W;
   t.mode = who;
-  hipError_t e = upload(&t.tape, tab.data(), rows);
-  if (e == hipSuccess) e = upload(&t.tdesc, cdesc.data(), C);
+  hipError_t e = upload(t.tape, tab.data(), rows);
+  if (e == hipSuccess) e = upload(t.tdesc, cdesc.data(), C);
   if (!replay) {  // (null in a replay: no record has an edit)
-    if (e == hipSuccess) e = upload(&t.vedit, ved.data(), rows);
-    if (e == hipSuccess) e = upload(&t.vwords, vw.data(), words);
-    if (e == hipSuccess) e = upload(&t.vmask, masks, C * W);
+    if (e == hipSuccess) e = upload(t.vedit, ved.data(), rows);
+    if (e == hipSuccess) e = upload(t.vwords, vw.data(), words);
+    if (e == hipSuccess) e = upload(t.vmask, masks, C * W);
   }
-  return install_staged(b, t, e, replay ? "decision table" : "variant tables");
+  if (e != hipSuccess)  // (t goes, the batch keeps its previous tables)
+    return set_err(std::string(replay ? "decision table" : "variant tables") + ": " + hipGetErrorString(e));
+  install_tables(b, std::move(t));
+  return 0;
 }
 
 // Keyed decisions in any order: a counting sort by cluster makes cluster c's records the base tape
@@ -765,7 +764,7 @@ int mr_batch_set_decisions(mr_batch* b, const mr_decision* d, size_t n) {
   if (!b) return set_err("null batch");
   if (n && !d) return set_err("null decisions");
   HIPCHK(hipSetDevice(b->cfg.device));
-  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream.get()));
   if (!n) { drop_decisions(b); return 0; }
   return no_throw("decision table", [&] { return set_decisions_impl(b, d, n); });  // host staging
 }
@@ -800,7 +799,7 @@ static int variants_enter(mr_batch* b, bool drop) {
   if (b->cfg.flags & MR_F_RECORD) return set_err("variants on a MR_F_RECORD batch");
   if (!drop && b->sof) return set_err("variants on a batch with a seed list (mr_batch_set_seeds)");
   HIPCHK(hipSetDevice(b->cfg.device));
-  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream.get()));
   if (!drop) return 1;
   if (b->dec.mode == OWN_VARIANTS) drop_decisions(b);  // (another kind of table is not a variant's to drop)
   return 0;
@@ -834,52 +833,32 @@ int mr_batch_set_variant_masks(mr_batch* b, const uint32_t* masks) {
   if (!b) return set_err("null batch");
   if (b->dec.mode != OWN_VARIANTS) return set_err("mr_batch_set_variant_masks without variants");
   HIPCHK(hipSetDevice(b->cfg.device));
-  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream.get()));
   const size_t mw = (size_t)b->D.C * b->D.vW;
   if (!mw) return 0;
-  if (masks) HIPCHK(hipMemcpy(b->dec.vmask, masks, mw * sizeof(uint32_t), hipMemcpyHostToDevice));
-  else HIPCHK(hipMemset(b->dec.vmask, 0, mw * sizeof(uint32_t)));
+  if (masks) HIPCHK(hipMemcpy(b->dec.vmask.get(), masks, mw * sizeof(uint32_t), hipMemcpyHostToDevice));
+  else HIPCHK(hipMemset(b->dec.vmask.get(), 0, mw * sizeof(uint32_t)));
   return 0;
 }
 
-static int mr_batch_get_decisions_impl(mr_batch* b, uint32_t k, mr_decision* out, size_t cap, size_t* n) {
-  if (!b || !n) return set_err("null argument");
-  if (k >= b->D.C) return set_err("cluster out of range");
+// The recorded tapes of clusters [first, first + count), of each at most `limit` records: one copy of
+// the CS_TAPE row slice (the row is cluster-minor, so the slice is contiguous), a scan on the host,
+// one tape_pack_kernel launch into a scratch buffer that starts with the offsets, one copy back. The
+// host touches no record: the kernel is the one place where a tape row becomes an mr_decision.
+static int read_tapes(mr_batch* b, uint32_t first, uint32_t count, uint64_t* drawn, uint64_t* off,
+                      mr_decision* out, size_t cap, uint64_t limit) {
   HIPCHK(hipSetDevice(b->cfg.device));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  uint32_t used = 0;
-  HIPCHK(hipMemcpy(&used, b->D.cs32 + CS_IDX(CS_TAPE, k, b->D.C), 4, hipMemcpyDeviceToHost));
-  *n = used;
-  if (b->D.tape_mode != TAPE_RECORD || !out) return 0;
-  size_t m = used < b->D.dcap ? used : b->D.dcap;
-  if (m > cap) m = cap;
-  std::vector<uint4> rows(m);
-  if (m)
-    HIPCHK(hipMemcpy(rows.data(), b->dec.tape + (size_t)k * b->D.dcap, m * sizeof(uint4),
-                     hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < m; i++)
-    out[i] = mr_decision{k, (uint16_t)(rows[i].x >> 16), (uint16_t)(rows[i].x & 0xFFFFu), rows[i].y,
-                         rows[i].z, rows[i].w};
-  return 0;
-}
-
-// The recorded tapes of clusters [first, first + count): one copy of the CS_TAPE row slice (the row is
-// cluster-minor, so the slice is contiguous), a scan on the host, one tape_pack_kernel launch into a
-// scratch buffer that starts with the offsets, one copy back. The host touches no record.
-static int get_decisions_packed_impl(mr_batch* b, uint32_t first, uint32_t count, uint64_t* drawn,
-                                     uint64_t* off, mr_decision* out, size_t cap) {
-  if (!b || !off) return set_err("null argument");
-  if ((uint64_t)first + count > b->D.C) return set_err("clusters out of range");
-  HIPCHK(hipSetDevice(b->cfg.device));
-  HIPCHK(hipStreamSynchronize(b->stream));
+  hipStream_t stream = b->stream.get();
+  HIPCHK(hipStreamSynchronize(stream));
   const uint32_t* used_d = b->D.cs32 + CS_IDX(CS_TAPE, first, b->D.C);
   std::vector<uint32_t> used(count);
   if (count) HIPCHK(hipMemcpy(used.data(), used_d, (size_t)count * 4, hipMemcpyDeviceToHost));
-  const bool rec = b->D.tape_mode == TAPE_RECORD;  // (with decisions set the counts are misses: no records)
+  // (with decisions set the counts are misses: no records)
+  const uint64_t keep = b->D.tape_mode == TAPE_RECORD ? std::min<uint64_t>(b->D.dcap, limit) : 0u;
   off[0] = 0;
   for (size_t i = 0; i < count; i++) {
     if (drawn) drawn[i] = used[i];
-    off[i + 1] = off[i] + (rec ? std::min(used[i], b->D.dcap) : 0u);
+    off[i + 1] = off[i] + std::min<uint64_t>(used[i], keep);
   }
   const uint64_t total = off[count];
   if (!out || !total) return 0;
@@ -887,19 +866,37 @@ static int get_decisions_packed_impl(mr_batch* b, uint32_t first, uint32_t count
     return set_err("mr_batch_get_decisions_packed: out holds " + std::to_string(cap) + " records, " +
                    std::to_string(total) + " are kept");
   const size_t head = ((size_t)(count + 1) * sizeof(uint64_t) + 255) & ~size_t(255);
-  char* scratch = nullptr;
-  HIPCHK(hipMalloc(&scratch, head + total * sizeof(mr_decision)));
-  hipError_t e = hipMemcpyAsync(scratch, off, (size_t)(count + 1) * sizeof(uint64_t),
-                                hipMemcpyHostToDevice, b->stream);
+  DevMem<char> scratch;
+  HIPCHK(dev_alloc(scratch, head + total * sizeof(mr_decision)));
+  char* recs = scratch.get() + head;
+  hipError_t e = hipMemcpyAsync(scratch.get(), off, (size_t)(count + 1) * sizeof(uint64_t),
+                                hipMemcpyHostToDevice, stream);
   if (e == hipSuccess)
-    e = launch_tape_pack(b->dec.tape, used_d, b->D.dcap, first, count,
-                         reinterpret_cast<const uint64_t*>(scratch),
-                         reinterpret_cast<uint32_t*>(scratch + head), b->stream);
+    e = launch_tape_pack(b->dec.tape.get(), used_d, b->D.dcap, first, count,
+                         reinterpret_cast<const uint64_t*>(scratch.get()),
+                         reinterpret_cast<uint32_t*>(recs), stream);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(out, scratch + head, total * sizeof(mr_decision), hipMemcpyDeviceToHost, b->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-  (void)hipFree(scratch);
+    e = hipMemcpyAsync(out, recs, total * sizeof(mr_decision), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
   if (e != hipSuccess) return set_err(std::string("tape pack: ") + hipGetErrorString(e));
+  return 0;
+}
+
+static int get_decisions_packed_impl(mr_batch* b, uint32_t first, uint32_t count, uint64_t* drawn,
+                                     uint64_t* off, mr_decision* out, size_t cap) {
+  if (!b || !off) return set_err("null argument");
+  if ((uint64_t)first + count > b->D.C) return set_err("clusters out of range");
+  return read_tapes(b, first, count, drawn, off, out, cap, ~0ull);
+}
+
+// one cluster: the packed read-back of [k, k + 1) with the caller's cap as the limit, so *n tells
+// all it drew and out gets what fits
+static int mr_batch_get_decisions_impl(mr_batch* b, uint32_t k, mr_decision* out, size_t cap, size_t* n) {
+  if (!b || !n) return set_err("null argument");
+  if (k >= b->D.C) return set_err("cluster out of range");
+  uint64_t drawn = 0, off[2];
+  if (read_tapes(b, k, 1, &drawn, off, out, cap, cap) != 0) return -1;
+  *n = drawn;
   return 0;
 }
 
@@ -912,35 +909,36 @@ static int mr_replay_impl(const mr_cfg* cfg, const mr_decision* d, size_t n, mr_
   c.flags = (c.flags | MR_F_TRACE) & ~MR_F_RECORD;
   c.trace_clusters = 1;
   c.trace_cap = cap ? (uint32_t)cap : 1u;
-  mr_batch* b = nullptr;
-  int rc = mr_batch_create(&c, &b);
-  if (rc) return rc;
+  mr_batch* made = nullptr;
+  if (const int rc = mr_batch_create(&c, &made)) return rc;
+  const Batch b(made);
   std::vector<mr_decision> one(d, d + n);
   for (auto& r : one) r.cluster = 0;
   // keyed replay runs the MR_TAPE kernels even for an empty trace (every draw then misses)
   const mr_decision none{0, MR_DS_TESTER, 0xFFFFu, 0xFFFFFFFFu, 0u, 0u};
   if (one.empty()) one.push_back(none);
-  rc = mr_batch_set_decisions(b, one.data(), one.size());
   mr_run_stats st;
-  if (!rc) rc = mr_batch_run(b, 0, &st);
   uint16_t cd = 0;
   uint32_t t = 0;
-  if (!rc) rc = mr_batch_verdicts(b, &cd, &t, nullptr);
-  if (!rc && out && cap) rc = mr_trace_get(b, 0, out, cap, n_out);
-  else if (!rc) *n_out = 0;
   size_t ms = 0;
-  if (!rc && misses) rc = mr_batch_get_decisions(b, 0, nullptr, 0, &ms);
-  if (!rc && misses) *misses = ms;
-  if (!rc && code) *code = cd;
-  if (!rc && time_us) *time_us = t;
-  mr_batch_destroy(b);
-  return rc;
+  if (const int rc = mr_batch_set_decisions(b.get(), one.data(), one.size())) return rc;
+  if (const int rc = mr_batch_run(b.get(), 0, &st)) return rc;
+  if (const int rc = mr_batch_verdicts(b.get(), &cd, &t, nullptr)) return rc;
+  if (!out || !cap) *n_out = 0;
+  else if (const int rc = mr_trace_get(b.get(), 0, out, cap, n_out)) return rc;
+  if (misses) {
+    if (const int rc = mr_batch_get_decisions(b.get(), 0, nullptr, 0, &ms)) return rc;
+    *misses = ms;
+  }
+  if (code) *code = cd;
+  if (time_us) *time_us = t;
+  return 0;
 }
 
 void mr_batch_destroy(mr_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->cfg.device);
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
+  if (b->stream) (void)hipStreamSynchronize(b->stream.get());
 #ifdef MR_PROF
   if (b->base) {  // development profile: wave cycles per kernel section (mr_kernel.hip PROF_*)
     unsigned long long h[PROF_SLOTS];
@@ -951,19 +949,7 @@ void mr_batch_destroy(mr_batch* b) {
     }
   }
 #endif
-  if (b->base) (void)hipFree(b->base);
-  free_tables(b->dec);
-  // the seed list and the streaming held-cluster lists belong to the batch, not to its decision tables
-  if (b->sof) (void)hipFree(b->sof);
-  for (uint32_t h = 0; h < 2; h++)
-    if (b->held[h]) { (void)hipFree(b->held[h]); b->held[h] = nullptr; }
-  if (b->red) (void)hipFree(b->red);
-  if (b->h_remaining) (void)hipHostFree(b->h_remaining);
-  if (b->h_ctl0) (void)hipHostFree(b->h_ctl0);
-  if (b->ev0) (void)hipEventDestroy(b->ev0);
-  if (b->ev1) (void)hipEventDestroy(b->ev1);
-  if (b->stream) (void)hipStreamDestroy(b->stream);
-  delete b;
+  delete b;  // its owners release the memory, the events and last the stream
 }
 
 int mr_batch_create(const mr_cfg* cfg, mr_batch** out) {
@@ -989,22 +975,17 @@ int mr_batch_get_decisions_packed(mr_batch* b, uint32_t first, uint32_t count, u
 // them what a draw does (a list alone: TAPE_SEEDS; dropped without tables: the batch's pool / step kernel again)
 int mr_batch_set_seeds(mr_batch* b, const uint32_t* seed_cluster) {
   if (!b) return set_err("null batch");
-  if (b->submitted) return set_err("batch has a submitted step: mr_batch_finish it first");
+  if (b->run.submitted) return set_err("batch has a submitted step: mr_batch_finish it first");
   if (seed_cluster && b->dec.mode == OWN_VARIANTS)
     return set_err("a seed list on a batch with variants set");
   HIPCHK(hipSetDevice(b->cfg.device));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  uint32_t* list = nullptr;
-  if (seed_cluster) {
-    const hipError_t e = upload(&list, seed_cluster, (size_t)b->D.C);
-    if (e != hipSuccess) {
-      if (list) (void)hipFree(list);
+  HIPCHK(hipStreamSynchronize(b->stream.get()));
+  DevMem<uint32_t> list;
+  if (seed_cluster)
+    if (const hipError_t e = upload(list, seed_cluster, (size_t)b->D.C); e != hipSuccess)
       return set_err(std::string("seed list: ") + hipGetErrorString(e));
-    }
-  }
-  if (b->sof) (void)hipFree(b->sof);
-  b->sof = list;
-  b->D.sof = list;
+  b->sof = std::move(list);
+  b->D.sof = b->sof.get();
   b->D.tape_mode = tape_mode_of(b);
   return 0;
 }

@@ -141,6 +141,55 @@ def test_submit_finish_pipeline_equals_run(budget, monkeypatch):
         assert wc == gc
 
 
+@pytest.mark.parametrize("stream", [False, True])
+def test_submit_finish_equals_reset_run_over_chunks(stream, monkeypatch):
+    """192 clusters on 64 lanes are three chunks, or with MR_F_STREAM one chunk whose lanes claim
+    on; initial_election_2a takes about 300 events per cluster, so at 100 per launch the submitted
+    launch leaves clusters of its chunk unfinished and chunks behind them. finish() runs all of
+    them to the verdicts, digests and counters of reset + run, and leaves nothing to a run()."""
+    import numpy as np
+
+    from madraft_amd import _abi, sim
+    monkeypatch.setenv("MR_STEP_BUDGET", "100")
+    kw = dict(lanes=64, stream=stream)
+    with sim.Batch("initial_election_2a", 192, **kw) as ref, \
+            sim.Batch("initial_election_2a", 192, **kw) as b:
+        for s in (_abi.README_SEED, _abi.README_SEED + 7919):
+            ref.reset(s)
+            want = ref.run()
+            assert want["remaining"] == 0 and want["launches"] > (1 if stream else 3)
+            b.submit(s)
+            st, cnt = b.finish()
+            assert st["remaining"] == 0 and st["launches"] > (1 if stream else 3)
+            assert st["events"] == want["events"]
+            for x, y in zip(ref.verdicts(), b.verdicts()):
+                assert np.array_equal(x, y)
+            assert cnt == ref.counters() and cnt["done"] == 192
+            again = b.run()
+            assert again["remaining"] == 0 and again["launches"] == 0
+            assert b.counters() == cnt
+
+
+def test_trace_of_a_submitted_and_finished_batch_equals_runs():
+    """trace(k) waits for the batch's own stream like the other read-backs: a batch that was only
+    submitted and finished gives the trace, digests and applies of the same seed run with run()."""
+    import numpy as np
+
+    from madraft_amd import _abi, sim
+    seed = _abi.README_SEED + 5
+    with sim.Batch("initial_election_2a", 1, trace_clusters=1) as a, \
+            sim.Batch("initial_election_2a", 1, trace_clusters=1) as b:
+        a.reset(seed)
+        assert a.run()["remaining"] == 0
+        b.submit(seed)
+        st, _ = b.finish()
+        assert st["remaining"] == 0
+        want = a.trace(0)
+        assert want.size > 0 and np.array_equal(b.trace(0), want)
+        assert np.array_equal(b.trace_digests(0), a.trace_digests(0))
+        assert np.array_equal(b.trace_applies(0), a.trace_applies(0))
+
+
 def _nccl_worker(port, q):
     import torch
     import torch.distributed as dist

@@ -172,6 +172,55 @@ def test_packed_tapes_at_a_small_tape_cap(hip):
         assert rc == 0 and np.array_equal(out, rec)
 
 
+def _one(hip, b, k, cap):
+    """mr_batch_get_decisions of position k into a marked buffer of cap + 2 records (cap None: a
+    NULL out): (n, the buffer's records that were written)."""
+    n = _abi.C.c_size_t()
+    if cap is None:
+        assert hip.lib().mr_batch_get_decisions(b._b, k, None, 0, _abi.C.byref(n)) == 0
+        return int(n.value), np.zeros(0, _abi.DECISION_DTYPE)
+    out = np.zeros(cap + 2, _abi.DECISION_DTYPE)
+    out["seq"], out["cluster"] = 0xABCDEF01, 0xFFFFFFFF
+    assert hip.lib().mr_batch_get_decisions(b._b, k, out.ctypes.data, cap, _abi.C.byref(n)) == 0
+    written = np.nonzero(out["cluster"] != 0xFFFFFFFF)[0]
+    assert written.tolist() == list(range(written.size))  # a prefix, and nothing past it
+    return int(n.value), out[: written.size]
+
+
+def test_one_position_read_back_is_the_packed_ones_row(hip):
+    """mr_batch_get_decisions is the packed read-back of one position: at a tape_cap below, at and
+    above what the three positions drew (56, 70, 64 against 64), for a NULL out and caps around
+    tape_cap, n is all the position drew and the records are decisions_all()'s row cut to the
+    cap. With decisions set n is the misses, and no record comes back."""
+    pos = POS[:3]
+    counts = [_small(k)[0] for k in pos]
+    assert counts[0] < SMALL_CAP < counts[1] and counts[2] == SMALL_CAP, counts
+    with _batch(hip, "figure_8", 3, flags=_abi.MR_F_RECORD, tape_cap=SMALL_CAP,
+                max_events=SMALL_EVENTS) as b:
+        b.set_seeds([SEED + k for k in pos])
+        _run(b)
+        drawn, off, rec = b.decisions_all()
+        assert drawn.tolist() == counts
+        for c in range(3):
+            row = rec[int(off[c]): int(off[c + 1])]
+            assert row.size == min(counts[c], SMALL_CAP)
+            for cap in (None, 1, SMALL_CAP - 1, SMALL_CAP, SMALL_CAP + 3):
+                n, got = _one(hip, b, c, cap)
+                assert n == counts[c], (c, cap)
+                assert np.array_equal(got, row[: min(cap or 0, SMALL_CAP)]), (c, cap)
+    tapes = [_halved(k, c) for c, k in enumerate(pos)]
+    with _batch(hip, "figure_8", 3) as b:
+        b.set_seeds([SEED + k for k in pos])
+        b.set_decisions(np.concatenate(tapes))
+        _run(b)
+        misses = b.decisions_all()[0]
+        assert all(int(m) > 0 for m in misses)
+        for c in range(3):
+            for cap in (None, 1, SMALL_CAP + 3):
+                n, got = _one(hip, b, c, cap)
+                assert n == int(misses[c]) and got.size == 0, (c, cap)
+
+
 def _halved(k, pos):
     """Seed k's recorded tape with every second record removed, for position pos."""
     return _positional(vu.recorded("figure_8", k)[0][::2], pos)
