@@ -168,7 +168,8 @@ constexpr uint32_t KSTR = MR_POOL ? POOL_SLOTS : STEP_BLOCK;
 // flight (config 4's peak is 28 per 512 seeds). (The 3- / 5-server pools run M <= 32.)
 constexpr bool KEYS_HBM = MR_POOL == 1 && NB > 5;
 constexpr uint32_t KROWS = KEYS_HBM ? 32u : 0xFFFFFFFFu;
-DI uint32_t key_rows(const Dev& D) { return D.M < KROWS ? D.M : KROWS; }  // LDS layout
+constexpr uint32_t key_rows(uint32_t M) { return M < KROWS ? M : KROWS; }  // LDS rows of M slots
+DI uint32_t key_rows(const Dev& D) { return key_rows(D.M); }
 DI uint32_t key_live(const Dev& D) {  // rows in use: slots below hold their key in LDS
   if constexpr (KEYS_HBM) return D.krows < key_rows(D) ? D.krows : key_rows(D);
   return key_rows(D);
@@ -197,8 +198,26 @@ DI void lk_set(const Dev& D, const X& x, uint32_t s, lkey_t v) {
 // the send loop's next[p] / term at next[p] - 1, the appliers' and the AppendEntries receive's
 // exchange words
 constexpr uint32_t WSTG_ROWS = 2 * MR_MAX_NODES;
+// The block's dynamic LDS, said once: word (u32) offsets from s_keys_raw and the total. The key
+// rows [rows][KSTR] (LK) come first, then the staging of the block's KSTR / 64 waves; the pool
+// units, which pass their record's words and their kinds (mr_pool.inc: PX_W, PK__N), go on with
+// the cluster records [px_w][KSTR], the queues' {head, tail} pairs (8-B aligned: every term
+// before them is a multiple of KSTR), the queues' entries [pk_n][KSTR], and the live count with a
+// pad word that keeps the total a multiple of 8 B
+struct LdsLayout { uint32_t stg, xr, qc, q, live, total; };
+constexpr LdsLayout lds_layout(uint32_t rows, uint32_t px_w = 0, uint32_t pk_n = 0) {
+  LdsLayout l{};
+  l.stg = rows * KSTR * (uint32_t)(sizeof(lkey_t) / 4u);
+  l.xr = l.stg + KSTR / 64u * WSTG_ROWS * 64u;
+  l.qc = l.xr + px_w * KSTR;
+  l.q = l.qc + 2u * pk_n;
+  l.live = l.q + pk_n * KSTR;
+  l.total = l.live + (pk_n ? 2u : 0u);
+  return l;
+}
+DI uint32_t* lds_words() { return reinterpret_cast<uint32_t*>(s_keys_raw); }
 DI uint32_t* wstg(const Dev& D) {
-  return reinterpret_cast<uint32_t*>(s_keys + key_rows(D) * KSTR) + (threadIdx.x >> 6) * (WSTG_ROWS * 64u);
+  return lds_words() + lds_layout(key_rows(D)).stg + (threadIdx.x >> 6) * (WSTG_ROWS * 64u);
 }
 DI uint32_t lane64() { return threadIdx.x & 63u; }
 #define LNX(p) wstg(D)[(p) * 64u + lane64()]
@@ -2450,10 +2469,9 @@ hipError_t launch_reduce(const Dev& D, unsigned long long* out, uint64_t cluster
 }
 #endif  // MR_COMMON
 
-// the step kernel's dynamic LDS: the message keys, then the per-wave staging (wstg)
-constexpr size_t step_lds_bytes(uint32_t M) {
-  return (size_t)M * STEP_BLOCK * sizeof(lkey_t) + WSTG_ROWS * STEP_BLOCK * sizeof(uint32_t);
-}
+// the step kernel's dynamic LDS: the message keys, then the per-wave staging (lds_layout)
+static_assert(MR_POOL || KSTR == STEP_BLOCK, "the step kernel's layout: one column per lane of its block");
+constexpr size_t step_lds_bytes(uint32_t M) { return (size_t)lds_layout(M).total * 4u; }  // (not in pool units)
 template <uint32_t S, uint32_t NBT>
 hipError_t launch_step_t(const Dev& D, uint32_t budget, hipStream_t s) {
   dim3 blk(STEP_BLOCK), grd((D.L + D.lpw - 1) / D.lpw);

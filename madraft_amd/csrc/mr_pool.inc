@@ -5,7 +5,7 @@
 // union of the paths its 64 clusters' next events take (measured: 12.9 of 64 lanes active per
 // VALU instruction). Here a workgroup of POOL_WAVES waves (two per SIMD) owns a pool of up to
 // POOL_SLOTS clusters. Between its events a cluster's run state — what step_kernel keeps in
-// registers — is a record in LDS (PX_*), its message keys a column of the LDS key rows, and its
+// registers — is a record in LDS (px_record), its message keys a column of the LDS key rows, and its
 // slot an entry in the queue of its next event's kind (PK_*: a tester step, an AppendEntries
 // request delivery, any other node event). A wave that is free reads the queues' lengths, takes up
 // to 64 ready clusters of one kind (a compare-and-swap of the queue's head: an entry is claimed by
@@ -36,19 +36,9 @@
 // the two counters read per cluster (leaders elected: the coverage histogram; the largest
 // applied index: the leader-completeness check) travel in the cluster's record.
 
-enum : uint32_t {
-  PX_C, PX_NOW, PX_EVENTS, PX_MSGS, PX_TCTR, PX_TWAKE, PX_TRACEN, PX_DIGLO, PX_DIGHI, PX_MMIN,
-  PX_FREE, PX_A /* code | inflight << 16 | mslot << 24 */, PX_B /* netmode | conn << 8 | alive << 16
-  | lmask << 24 */, PX_LEAD, PX_MAXI, PX_EVEND /* the launch's event budget ends here */,
-  PX_SVC /* the service pool: free slots 32..63, AppendEntries slots (2), cwake, ctid, cslot, and
-  the connected hosts (clerk hosts 8 + k too: PX_B keeps servers 0..7 only); the 7-server Raft
-  pool (KEYS_HBM): free slots 32..63 */
-};
-// the service pool's applier continuation (x.ap0..ap3, node_event AP_CAP) after its 7 words
-constexpr uint32_t PX_AP = PX_SVC + 7u;
-constexpr uint32_t PX_TMR = PX_SVC + (MR_POOL == 2 ? 11u : KEYS_HBM ? 1u : 0u);
-constexpr uint32_t PX_W = PX_TMR + NB;
-constexpr uint32_t PX_EMPTY = ~0u;  // PX_C of a slot that holds no cluster
+// The record's words are the rows of px_record below, the one description that the store, the load
+// and the word count PX_W walk. Word 0 is the cluster id; PX_EMPTY there: the slot holds no cluster
+constexpr uint32_t PX_EMPTY = ~0u;
 // bins: a tester step (PK_TESTER); an AppendEntries request delivery (key bit 3, PK_AE); every
 // other node event (PK_NODE); and, for test bodies that crash and restart servers
 // (restarts_servers), bins of their own for RequestVote request / reply deliveries (key bit 4),
@@ -82,121 +72,126 @@ static_assert((1u << PSB) == POOL_SLOTS, "queue positions wrap at the pool size"
 // figure_8_unreliable_2c 104.3 -> 102.8 ms, its crash variant 43.40 -> 41.75 ms, VALU
 // instructions per event 40.1 -> 34.9.
 //
-// LDS after the key rows [M][POOL_SLOTS] and the per-wave staging (wstg)
+// LDS after the key rows [key_rows][POOL_SLOTS] and the per-wave staging (mr_kernel.hip: lds_layout)
 struct PoolL {
   uint32_t* xr;    // [PX_W][POOL_SLOTS] cluster records
   uint32_t* qc;    // [PK__N][2] the queues' head and tail positions (8-B aligned pairs)
   uint32_t* q;     // [PK__N][PS] queue entries: lap << 16 | slot
   uint32_t* live;  // clusters running and within the launch's budget
 };
-DI PoolL pool_l(const Dev& D) {
-  uint32_t* p = reinterpret_cast<uint32_t*>(s_keys + key_rows(D) * KSTR) + POOL_WAVES * WSTG_ROWS * 64u;
-  PoolL L;
-  L.xr = p;
-  p += PX_W * PS;
-  L.qc = p;
-  p += 2u * PK__N;
-  L.q = p;
-  p += PK__N * PS;
-  L.live = p;
-  return L;
-}
-constexpr size_t pool_lds_bytes(uint32_t M) {
-  return ((size_t)(M < KROWS ? M : KROWS) * PS + POOL_WAVES * WSTG_ROWS * 64u + PX_W * PS + 2u * PK__N +
-          PK__N * PS + 2u) * 4u;
-}
-DI unsigned long long qc_pair(const PoolL& L, uint32_t k) {  // {head, tail} of kind k, one 8-B load
-  return __hip_atomic_load(reinterpret_cast<unsigned long long*>(L.qc) + k, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
+// A walk of the record: PX_PUT stores the lane's registers to its slot's column r[word * PS],
+// PX_GET loads them, PX_COUNT only counts the words. bits(f, w) is the one primitive: the next w
+// bits of the current word hold f (w = 32: a whole word); the others are encodings on top of it
+enum PxMode { PX_PUT, PX_GET, PX_COUNT };
+// mmin (32-bit keys: t << 32 | the key's low five bits, ~0 = no message) as one word: the key
+constexpr uint32_t mmin_pack(uint64_t m) { return m == ~0ull ? ~0u : ((uint32_t)(m >> 32) << 5) | ((uint32_t)m & 31u); }
+constexpr uint64_t mmin_unpack(uint32_t w) { return w == ~0u ? ~0ull : ((uint64_t)(w >> 5) << 32) | (w & 31u); }
+template <PxMode M>
+struct Px {
+  uint32_t* r = nullptr;
+  uint32_t n = 0, sh = 0, cur = 0;  // words done, bits done of the current word, that word
+  bool ok = true;                   // (PX_COUNT) no field straddles a word
+  // (cut: f may hold higher bits, which the record drops; otherwise f fits its w bits as it is)
+  template <class T>
+  constexpr __forceinline__ void bits(T& f, uint32_t w, bool cut = false) {
+    const uint32_t m = w < 32u ? (1u << w) - 1u : ~0u;
+    if constexpr (M == PX_GET) {
+      if (sh == 0u) cur = r[n * PS];
+      f = (cur >> sh) & m;
+    }
+    if constexpr (M == PX_PUT) cur |= (cut ? (uint32_t)f & m : (uint32_t)f) << sh;
+    if constexpr (M == PX_COUNT) ok = ok && sh + w <= 32u;
+    if ((sh += w) < 32u) return;
+    if constexpr (M == PX_PUT) r[n * PS] = cur;
+    n++;
+    sh = cur = 0u;
+  }
+  template <class... T>
+  constexpr __forceinline__ void words(T&... f) { (bits(f, 32u), ...); }  // a whole word each
+  template <class T>
+  constexpr __forceinline__ void half(T& f, uint32_t s) {  // bits s .. s + 31 of a 64-bit value
+    uint32_t w = 0u;
+    if constexpr (M == PX_PUT) w = (uint32_t)(f >> s);
+    bits(w, 32u);
+    if constexpr (M == PX_GET) f = s ? f | (uint64_t)w << 32 : (uint64_t)w;
+  }
+  template <class T>
+  constexpr __forceinline__ void wide(T& f) { half(f, 0u), half(f, 32u); }  // 64 bits: low, high
+  template <class T>
+  constexpr __forceinline__ void mmin(T& f) {
+    uint32_t w = 0u;
+    if constexpr (M == PX_PUT) w = mmin_pack(f);
+    bits(w, 32u);
+    if constexpr (M == PX_GET) f = mmin_unpack(w);
+  }
+  constexpr void reserve(uint32_t words) { n += words; }
+};
+// THE RECORD: what a pool slot keeps of its cluster between two events (X, and the launch's budget
+// end), row by row in the order of its words. Every position, width and condition is here only
+template <uint32_t S, class V, class XT>
+constexpr __forceinline__ void px_record(V& v, XT& x, uint32_t& evend) {
+  // (word 0, the cluster id: PX_EMPTY, px_clear / px_held)
+  v.words(x.c, x.now, x.events, x.msgs_sent, x.t_ctr, x.twake, x.trace_n);
+  v.wide(x.digest);
+  v.mmin(x.mmin);
+  v.half(x.free_mask[0], 0u);  // free message slots 0..31
+  v.bits(x.code, 16u, true), v.bits(x.inflight, 8u), v.bits(x.mslot, 8u);
+  // (conn: servers 0..7 only; the service pool keeps its clerk hosts', 8 + k, in the whole word below)
+  v.bits(x.netmode, 8u), v.bits(x.conn, 8u, true), v.bits(x.alive, 8u), v.bits(x.lmask, 8u);
+  // the two counters that travel; where the launch's event budget ends for the cluster
+  v.words(x.cnt[CNT_LEADERS], x.cnt[CNT_MAX_INDEX], evend);
+  constexpr bool SVC = MR_POOL == 2;
+  if constexpr (KEYS_HBM || SVC) v.half(x.free_mask[0], 32u);  // free message slots 32..63
+  if constexpr (SVC) {
+    v.wide(x.aem);
+    v.words(x.cwake, x.ctid, x.cslot, x.conn);
+    if constexpr (ap_cont(S)) v.words(x.ap0, x.ap1, x.ap2, x.ap3);  // (node_event AP_CAP)
+    else v.reserve(4u);  // (the continuation's words stay: one PX_W per unit)
+  }
+#pragma unroll
+  for (uint32_t d = 0; d < NB; d++) v.bits(x.timer[d], 32u);
+}
+template <uint32_t S>
+constexpr Px<PX_COUNT> px_count() {
+  Px<PX_COUNT> v{};
+  X x{};
+  uint32_t evend = 0;
+  px_record<S>(v, x, evend);
+  return v;
+}
+static_assert(px_count<0>().ok && px_count<0>().sh == 0u, "px_record: the fields of a shared word fill its 32 bits");
+constexpr uint32_t PX_W = px_count<0>().n;  // (the same for every scenario: pool_kernel asserts it)
 // registers <-> the cluster's LDS record (x.ls is its slot)
 template <uint32_t S>
 DI void px_put(const PoolL& L, const X& x, uint32_t evend) {
-  uint32_t* r = L.xr + x.ls;
-  const uint32_t m32 = x.mmin == ~0ull ? ~0u : ((uint32_t)(x.mmin >> 32) << 5) | ((uint32_t)x.mmin & 31u);
-  r[PX_C * PS] = x.c;
-  r[PX_NOW * PS] = x.now;
-  r[PX_EVENTS * PS] = x.events;
-  r[PX_MSGS * PS] = x.msgs_sent;
-  r[PX_TCTR * PS] = x.t_ctr;
-  r[PX_TWAKE * PS] = x.twake;
-  r[PX_TRACEN * PS] = x.trace_n;
-  r[PX_DIGLO * PS] = (uint32_t)x.digest;
-  r[PX_DIGHI * PS] = (uint32_t)(x.digest >> 32);
-  r[PX_MMIN * PS] = m32;
-  r[PX_FREE * PS] = (uint32_t)x.free_mask[0];
-  r[PX_A * PS] = (x.code & 0xFFFFu) | (x.inflight << 16) | (x.mslot << 24);
-  r[PX_B * PS] = x.netmode | ((x.conn & 255u) << 8) | (x.alive << 16) | (x.lmask << 24);
-  r[PX_LEAD * PS] = x.cnt[CNT_LEADERS];
-  r[PX_MAXI * PS] = x.cnt[CNT_MAX_INDEX];
-  r[PX_EVEND * PS] = evend;
-  if constexpr (KEYS_HBM) r[PX_SVC * PS] = (uint32_t)(x.free_mask[0] >> 32);
-  if constexpr (MR_POOL == 2) {
-    r[PX_SVC * PS] = (uint32_t)(x.free_mask[0] >> 32);
-    r[(PX_SVC + 1) * PS] = (uint32_t)x.aem;
-    r[(PX_SVC + 2) * PS] = (uint32_t)(x.aem >> 32);
-    r[(PX_SVC + 3) * PS] = x.cwake;
-    r[(PX_SVC + 4) * PS] = x.ctid;
-    r[(PX_SVC + 5) * PS] = x.cslot;
-    r[(PX_SVC + 6) * PS] = x.conn;
-    if constexpr (ap_cont(S)) {
-      r[PX_AP * PS] = x.ap0;
-      r[(PX_AP + 1) * PS] = x.ap1;
-      r[(PX_AP + 2) * PS] = x.ap2;
-      r[(PX_AP + 3) * PS] = x.ap3;
-    }
-  }
-#pragma unroll
-  for (uint32_t d = 0; d < NB; d++) r[(PX_TMR + d) * PS] = x.timer[d];
+  Px<PX_PUT> v{L.xr + x.ls};
+  px_record<S>(v, x, evend);
 }
 template <uint32_t S>
-DI uint32_t px_get(const PoolL& L, X& x) {  // returns the budget end (PX_EVEND)
-  const uint32_t* r = L.xr + x.ls;
-  x.c = r[PX_C * PS];
-  x.now = r[PX_NOW * PS];
-  x.events = r[PX_EVENTS * PS];
-  x.msgs_sent = r[PX_MSGS * PS];
-  x.t_ctr = r[PX_TCTR * PS];
-  x.twake = r[PX_TWAKE * PS];
-  x.trace_n = r[PX_TRACEN * PS];
-  x.digest = ((uint64_t)r[PX_DIGHI * PS] << 32) | r[PX_DIGLO * PS];
-  const uint32_t m32 = r[PX_MMIN * PS];
-  x.mmin = m32 == ~0u ? ~0ull : ((uint64_t)(m32 >> 5) << 32) | (m32 & 31u);
-  x.free_mask[0] = r[PX_FREE * PS];
-  const uint32_t a = r[PX_A * PS], b = r[PX_B * PS];
-  x.code = a & 0xFFFFu;
-  x.inflight = (a >> 16) & 255u;
-  x.mslot = a >> 24;
-  x.netmode = b & 255u;
-  x.conn = (b >> 8) & 255u;
-  x.alive = (b >> 16) & 255u;
-  x.lmask = b >> 24;
-  x.cnt[CNT_LEADERS] = r[PX_LEAD * PS];
-  x.cnt[CNT_MAX_INDEX] = r[PX_MAXI * PS];
-#pragma unroll
-  for (uint32_t d = 0; d < NB; d++) x.timer[d] = r[(PX_TMR + d) * PS];
-  if constexpr (KEYS_HBM) x.free_mask[0] |= (uint64_t)r[PX_SVC * PS] << 32;
-  if constexpr (MR_POOL == 2) {
-    x.free_mask[0] |= (uint64_t)r[PX_SVC * PS] << 32;
-    x.aem = ((uint64_t)r[(PX_SVC + 2) * PS] << 32) | r[(PX_SVC + 1) * PS];
-    x.cwake = r[(PX_SVC + 3) * PS];
-    x.ctid = r[(PX_SVC + 4) * PS];
-    x.cslot = r[(PX_SVC + 5) * PS];
-    x.conn = r[(PX_SVC + 6) * PS];
-    if constexpr (ap_cont(S)) {
-      x.ap0 = r[PX_AP * PS];
-      x.ap1 = r[(PX_AP + 1) * PS];
-      x.ap2 = r[(PX_AP + 2) * PS];
-      x.ap3 = r[(PX_AP + 3) * PS];
-    } else {
-      x.ap0 = 0u;
-    }
-  } else {
-    x.cwake = INF_T; x.ctid = 0; x.cslot = 0;
-  }
+DI uint32_t px_get(const PoolL& L, X& x) {  // returns the launch's budget end
+  // what no record holds: said here, and the rows whose condition holds load over it
   x.sleep_us = 0; x.yield = 0;
-  return r[PX_EVEND * PS];
+  x.cwake = INF_T; x.ctid = 0; x.cslot = 0; x.ap0 = 0;
+  Px<PX_GET> v{L.xr + x.ls};
+  uint32_t evend = 0;
+  px_record<S>(v, x, evend);
+  return evend;
+}
+DI void px_clear(const PoolL& L, uint32_t slot) { L.xr[slot] = PX_EMPTY; }
+DI bool px_held(const PoolL& L, uint32_t slot) { return L.xr[slot] != PX_EMPTY; }
+// a launch's budget for a cluster that enters it at x.events
+DI uint32_t budget_end(const X& x, uint32_t budget) { return x.events > ~0u - budget ? ~0u : x.events + budget; }
+
+constexpr LdsLayout pool_layout(uint32_t M) { return lds_layout(key_rows(M), PX_W, PK__N); }
+DI PoolL pool_l(const Dev& D) {
+  const LdsLayout l = pool_layout(D.M);
+  return PoolL{lds_words() + l.xr, lds_words() + l.qc, lds_words() + l.q, lds_words() + l.live};
+}
+constexpr size_t pool_lds_bytes(uint32_t M) { return (size_t)pool_layout(M).total * 4u; }
+DI unsigned long long qc_pair(const PoolL& L, uint32_t k) {  // {head, tail} of kind k, one 8-B load
+  return __hip_atomic_load(reinterpret_cast<unsigned long long*>(L.qc) + k, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 // the kind (the queue) of the cluster's next event, which next_event chose
@@ -264,6 +259,9 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
   static_assert(MR_POOL == 2 ? is_svc(S) : nthr(S) == 0 && !is_svc(S),
                 "MR_POOL 1 units run Raft-only test bodies, MR_POOL 2 units the service ones");
   static_assert(EXACT_N, "exact-size instances only (has_pool)");
+  static_assert(pool_lds_bytes(pool_max_slots(S, NB)) <= 160u * 1024u,
+                "the pool's LDS passes the CU's 160 KiB: a record word (px_record) costs 4 * POOL_SLOTS bytes");
+  static_assert(px_count<S>().n == PX_W, "px_record: the record's width does not depend on the scenario");
   Dev D = Din;
   fix_scenario<S>(D);
   const PoolL P = pool_l(D);
@@ -291,9 +289,9 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
     uint32_t kd = 0;
     if (held) {
       kd = pool_kind<S>(x);
-      px_put<S>(P, x, x.events > ~0u - budget ? ~0u : x.events + budget);
+      px_put<S>(P, x, budget_end(x, budget));
     } else {
-      P.xr[PX_C * PS + tid] = PX_EMPTY;
+      px_clear(P, tid);
     }
     pool_publish(P, held, kd, tid);
     const uint32_t nh = (uint32_t)__popcll(__ballot(held));
@@ -372,9 +370,9 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
       x.ls = slot;
       if (got_new) {
         cont = true;
-        px_put<S>(P, x, x.events > ~0u - budget ? ~0u : x.events + budget);
+        px_put<S>(P, x, budget_end(x, budget));
       } else {
-        P.xr[PX_C * PS + slot] = PX_EMPTY;
+        px_clear(P, slot);
       }
     } else {
       px_put<S>(P, x, evend);
@@ -415,7 +413,7 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
   // epilogue: every slot's cluster back to HBM (still running: counted, and resumed first by the
   // next launch of a streaming batch)
   x.ls = tid;
-  if (P.xr[PX_C * PS + tid] != PX_EMPTY) {
+  if (px_held(P, tid)) {
     px_get<S>(P, x);
     launch_end<S>(D, x);
   }
