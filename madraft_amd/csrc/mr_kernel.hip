@@ -24,6 +24,7 @@
 #include <atomic>
 
 #include "mr_dev.h"
+#include "mr_qentry.h"
 
 #ifndef MR_TAPE
 #define MR_TAPE 0
@@ -2180,23 +2181,33 @@ DI void launch_end(const Dev& D, X& x) {
 constexpr uint32_t KEY_DST = MR_POOL == 1 ? 7u : 31u;
 // the cluster's next event: the minimum (time, class, tie) key over the tester wake-up, the
 // earliest spawned thread (tcli), the node timers and the earliest message
+// The key of the event a decision (cls, node, tcli) names: the one place that says it. next_event
+// compares these keys; the pool's claimer, which reads the decision from its queue entry
+// (mr_pool.inc), takes the chosen event's key from here without comparing again
+template <uint32_t S>
+DI uint64_t event_key(const X& x, uint32_t cls, uint32_t node, bool tcli) {
+  if (cls == CLS_MSG) return x.mmin;
+  if (cls == CLS_TIMER) return ((uint64_t)sel_nb(x.timer, node) << 32) | (1ull << 30) | node;
+  if (nthr(S) > 0 && tcli) return ((uint64_t)x.cwake << 32) | (2ull << 30) | x.ctid;  // (tie = tid)
+  return ((uint64_t)x.twake << 32) | (2ull << 30);
+}
 template <uint32_t S>
 DI void next_event(const X& x, uint64_t& key, uint32_t& cls, uint32_t& node, bool& tcli) {
-  key = ((uint64_t)x.twake << 32) | (2ull << 30);
+  key = event_key<S>(x, CLS_TESTER, 0u, false);
   cls = CLS_TESTER;
   node = 0;
   tcli = false;
-  if constexpr (nthr(S) > 0) {  // the earliest spawned thread (tie = tid)
-    const uint64_t kc = ((uint64_t)x.cwake << 32) | (2ull << 30) | x.ctid;
+  if constexpr (nthr(S) > 0) {  // the earliest spawned thread
+    const uint64_t kc = event_key<S>(x, CLS_TESTER, 0u, true);
     tcli = kc < key;
     if (tcli) key = kc;
   }
 #pragma unroll
   for (uint32_t d = 0; d < NB; d++) {  // timers of absent nodes are INF_T
-    const uint64_t kt = ((uint64_t)x.timer[d] << 32) | (1ull << 30) | d;
+    const uint64_t kt = event_key<S>(x, CLS_TIMER, d, false);
     if (kt < key) { key = kt; cls = CLS_TIMER; node = d; }
   }
-  if (x.mmin < key) { key = x.mmin; cls = CLS_MSG; node = (uint32_t)key & KEY_DST; }
+  if (x.mmin < key) { key = event_key<S>(x, CLS_MSG, 0u, false); cls = CLS_MSG; node = (uint32_t)key & KEY_DST; }
 }
 // the event next_event chose runs (seq: a 64-bit message key's sequence number)
 template <uint32_t S>

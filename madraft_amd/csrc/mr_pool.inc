@@ -7,7 +7,8 @@
 // POOL_SLOTS clusters. Between its events a cluster's run state — what step_kernel keeps in
 // registers — is a record in LDS (px_record), its message keys a column of the LDS key rows, and its
 // slot an entry in the queue of its next event's kind (PK_*: a tester step, an AppendEntries
-// request delivery, any other node event). A wave that is free reads the queues' lengths, takes up
+// request delivery, any other node event); the entry, lap << 16 | decision | slot (mr_qentry.h),
+// also names that event (class, node, spawned thread), decided once, when it is published. A wave that is free reads the queues' lengths, takes up
 // to 64 ready clusters of one kind (a compare-and-swap of the queue's head: an entry is claimed by
 // exactly one wave), runs their events with the state in registers through the same handlers as
 // step_kernel, and publishes each cluster's next kind. A cluster runs on one lane at a time, its events in its own order, so
@@ -60,12 +61,21 @@ static_assert(PK__N <= 8, "MR_PROF keeps 8 kinds of statistics");
 template <uint32_t S>
 constexpr bool pool_fine_bins() { return restarts_servers(S); }
 constexpr uint32_t PS = POOL_SLOTS;
-constexpr uint32_t PSB = POOL_SLOTS == 512 ? 9u : 8u;  // log2(PS)
-static_assert((1u << PSB) == POOL_SLOTS, "queue positions wrap at the pool size");
+// a queue entry (mr_qentry.h): the slot, next_event's decision for the cluster's next event, and
+// the lap tag. The fields hold what this unit's next_event can choose
+using QE = QEntry<MR_POOL>;
+static_assert(QE::SLOT_N == POOL_SLOTS, "queue positions wrap at the pool size");
+static_assert(CLS_MSG < QE::CLS_N && CLS_TIMER < QE::CLS_N && CLS_TESTER < QE::CLS_N, "an entry's class field");
+static_assert(NB <= QE::NODE_N && KEY_DST < QE::NODE_N, "an entry's node field: a timer's server, a key's destination");
+static_assert(MR_POOL == 2 || QE::TCLI_B == 0u, "the Raft pool runs no spawned threads (pool_kernel asserts nthr)");
+static_assert(MR_POOL != 2 || CLERK_HOST + 16u <= QE::NODE_N, "the service pool's clerk hosts are nodes 8 ..");
 
 // The ready clusters of a kind are a FIFO ring of slot ids: per kind a {head, tail} pair of
 // positions and PS entries (a kind never holds more than the pool), each entry tagged with the
-// lap of its position so a stale one is never taken. A wave claims min(64, queued) entries of
+// lap of its position so a stale one is never taken. Between the tag and the slot an entry carries
+// what next_event decided when it was published (class, node, spawned thread: mr_qentry.h), so the
+// claiming wave runs that event with its key from the record (event_key) and does not decide again:
+// next_event runs once per event, in pool_kind, off the path from the claim to the event's loads. A wave claims min(64, queued) entries of
 // the fullest kind with one compare-and-swap of the head and lane i reads entry head + i; a wave
 // publishes its lanes' next kinds with one atomic add of a tail per kind present. Same-box A/B
 // against round 5's 512-bit bins with a per-wave claim list (r06_q, profiles/r06_ab_queue.txt):
@@ -76,7 +86,7 @@ static_assert((1u << PSB) == POOL_SLOTS, "queue positions wrap at the pool size"
 struct PoolL {
   uint32_t* xr;    // [PX_W][POOL_SLOTS] cluster records
   uint32_t* qc;    // [PK__N][2] the queues' head and tail positions (8-B aligned pairs)
-  uint32_t* q;     // [PK__N][PS] queue entries: lap << 16 | slot
+  uint32_t* q;     // [PK__N][PS] queue entries (QE): lap << 16 | decision | slot
   uint32_t* live;  // clusters running and within the launch's budget
 };
 
@@ -194,14 +204,15 @@ DI unsigned long long qc_pair(const PoolL& L, uint32_t k) {  // {head, tail} of 
                            __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// the kind (the queue) of the cluster's next event, which next_event chose
+// the cluster's next event, decided here and nowhere else in the pool: next_event's decision `dc`,
+// which travels in the queue entry to the wave that claims it, and its kind (the queue). The key
+// of a decision is event_key's (mr_kernel.hip), here and at the claim
 template <uint32_t S>
-DI uint32_t pool_kind(const X& x) {
+DI uint32_t pool_kind(const X& x, QDec& dc) {
   constexpr bool FINE = pool_fine_bins<S>();
   uint64_t key;
-  uint32_t cls, node;
-  bool tcli;
-  next_event<S>(x, key, cls, node, tcli);
+  next_event<S>(x, key, dc.cls, dc.node, dc.tcli);
+  const uint32_t cls = dc.cls, node = dc.node;
   if constexpr (ap_cont(S))
     if (x.ap0 >> 31) return PK_APPLY;  // the current event's applier continues (AP_CAP)
   if (cls == CLS_TESTER) return PK_TESTER;
@@ -230,12 +241,13 @@ DI uint32_t pool_pick(const uint32_t (&n)[PK__N]) {
     if (n[q] > n[k]) k = q;
   return k;
 }
-// the lanes with `pub` append their slots to the queue of their kind `kd`: one atomic add of the
+// the lanes with `pub` append their slots, with their next events' decisions `dc`, to the queue of
+// their kind `kd`: one atomic add of the
 // kind's tail per kind present, then each lane writes its entry at tail + its rank (a claimer that
 // reserved that position before the entry lands waits for its lap tag). The event's global stores
 // and the record's LDS writes land before another wave can claim the slot (workgroup scope: the
 // waves share the CU's vector L1)
-DI void pool_publish(const PoolL& L, bool pub, uint32_t kd, uint32_t slot) {
+DI void pool_publish(const PoolL& L, bool pub, uint32_t kd, const QDec& dc, uint32_t slot) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
 #pragma unroll
   for (uint32_t k = 0; k < PK__N; k++) {
@@ -247,7 +259,7 @@ DI void pool_publish(const PoolL& L, bool pub, uint32_t kd, uint32_t slot) {
     base = rl(base, ld);
     if (pub && kd == k) {
       const uint32_t pos = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-      __hip_atomic_store(&L.q[k * PS + (pos & (PS - 1u))], ((pos >> PSB) << 16) | slot, __ATOMIC_RELAXED,
+      __hip_atomic_store(&L.q[k * PS + (pos & (PS - 1u))], QE::pack(pos, slot, dc), __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_WORKGROUP);
     }
   }
@@ -287,13 +299,14 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
     x.ls = tid;
     const bool held = launch_begin<S>(D, x);
     uint32_t kd = 0;
+    QDec dc{};
     if (held) {
-      kd = pool_kind<S>(x);
+      kd = pool_kind<S>(x, dc);
       px_put<S>(P, x, budget_end(x, budget));
     } else {
       px_clear(P, tid);
     }
-    pool_publish(P, held, kd, tid);
+    pool_publish(P, held, kd, dc, tid);
     const uint32_t nh = (uint32_t)__popcll(__ballot(held));
     if (lane == 0 && nh) atomicAdd(P.live, nh);
   }
@@ -301,6 +314,7 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
   for (;;) {
     PROF(P_TAIL);
     uint32_t kind;
+    QDec dc{};  // the claimed cluster's event, as its publisher decided it
 #ifdef MR_PROF
     unsigned long long t_claim = 0;
 #endif
@@ -340,23 +354,21 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
         if (kind == k) { pst[k]++; pst[8 + k] += n; }
 #endif
       if (lane >= n) continue;
-      const uint32_t pos = h + lane, tag = (pos >> PSB) << 16;
+      const uint32_t pos = h + lane, tag = QE::tag_of(pos);
       uint32_t e;
       do {  // the publisher's entry write follows its tail add
         e = __hip_atomic_load(&P.q[kind * PS + (pos & (PS - 1u))], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      } while ((e & 0xFFFF0000u) != tag);
-      x.ls = e & 0xFFFFu;
+      } while (QE::tag(e) != tag);
+      x.ls = QE::slot(e);
+      dc = QE::dec(e);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     const uint32_t evend = px_get<S>(P, x);
     if (ap_cont(S) && (x.ap0 >> 31)) {  // not a new event: the current one's applier goes on
       node_event<S>(D, x, false, x.ap0 & 7u, 0u, 0u);
-    } else {
-      uint64_t key;
-      uint32_t cls, node;
-      bool tcli;
-      next_event<S>(x, key, cls, node, tcli);
-      run_event<S>(D, x, key, cls, node, tcli, 0u);  // (32-bit keys: no sequence number)
+    } else {  // the event the entry names: its key from the record, no second next_event
+      run_event<S>(D, x, event_key<S>(x, dc.cls, dc.node, dc.tcli), dc.cls, dc.node, dc.tcli,
+                   0u);  // (32-bit keys: no sequence number)
     }
     // the cluster back to the pool: its next kind's queue, or out of the running (a verdict, or
     // the launch's budget reached: the epilogue stores it)
@@ -377,7 +389,8 @@ __global__ void __launch_bounds__(POOL_SLOTS, POOL_WAVES / 4) pool_kernel(Dev Di
     } else {
       px_put<S>(P, x, evend);
     }
-    pool_publish(P, cont, cont ? pool_kind<S>(x) : 0u, x.ls);
+    const uint32_t kd = cont ? pool_kind<S>(x, dc) : 0u;
+    pool_publish(P, cont, kd, dc, x.ls);
 #ifdef MR_PROF
     {
       const unsigned long long dt = __shfl(wall_clock64() - t_claim, 0);
