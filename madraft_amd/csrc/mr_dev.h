@@ -90,12 +90,15 @@ constexpr uint32_t CS_STRIDE = (CS__N + 3u) & ~3u, C64_STRIDE = (C64__N + 1u) & 
 // range, 14..15 the snapshot value (u64), 16..23 next[p], 24..31 match[p]
 // (leader -> peer p). match[me] holds the leader's base: its last index when it
 // won its term (every entry above it, and none at or below, has the current
-// term). LASTT caches term_at(last). Node timers live in tmr [n][C].
+// term), or LBASE_NONE once it has taken entries or a snapshot from another leader of
+// its term (two leaders in a term: MR_F_BUG_VOTE_TWICE), after which no index tells an
+// entry's term. LASTT caches term_at(last). Node timers live in tmr [n][C].
 enum : uint32_t {
   NF_FLAGS, NF_TERM, NF_COMMIT, NF_APPLIED, NF_LAST, NF_SNAP, NF_SNAPT, NF_ECTR, NF_NCTR,
   NF_PEXP, NF_SLEN, NF_LASTT, NF_PLO, NF_PHI, NF_SNAPV, NF__N = 16
 };
 enum : uint32_t { PF_NEXT, PF_MATCH, PF__N };
+constexpr uint32_t LBASE_NONE = ~0u;
 constexpr uint32_t NR_PEER = 16;  // next[] at 16, match[] at 16 + MR_MAX_NODES
 constexpr uint32_t NREC = 32;
 // ms32 [C][M][MREC]: one 32-B record per in-flight message (value at 6..7);

@@ -1090,7 +1090,8 @@ DI void node_apply_coop(const Dev& D, X& x, uint32_t me, NC& d) {
 
 // commit = the majority-th largest of the match indices mv[] (mv[me] = last),
 // if that entry is from the current term: for a leader, exactly the entries
-// above its base lbase (mr_dev.h NF record note), so no log access
+// above its base lbase (mr_dev.h NF record note), so no log access — unless the leader has
+// no base (LBASE_NONE: it took entries from another leader of its term): then the entry's term
 DI void advance_commit(const Dev& D, X& x, uint32_t me, NC& d, const uint32_t (&mv)[NB],
                        uint32_t lbase) {
   uint32_t maj = D.n / 2 + 1, N = 0;
@@ -1101,7 +1102,8 @@ DI void advance_commit(const Dev& D, X& x, uint32_t me, NC& d, const uint32_t (&
     for (uint32_t j = 0; j < NB; j++) ge += (j < D.n && mv[j] >= mv[i]) ? 1u : 0u;
     if (i < D.n && ge >= maj && mv[i] > N) N = mv[i];
   }
-  if (N > d.commit && N > lbase) d.commit = N;  // term_at(N) == term
+  if (N > d.commit && (N > lbase || (lbase == LBASE_NONE && term_at(D, x, me, d, N) == d.term)))
+    d.commit = N;  // term_at(N) == term
 }
 
 // MR_F_SAFETY (SEMANTICS §11) when `me` wins term d.term:
@@ -1589,6 +1591,12 @@ DI void node_event(const Dev& Darg, X& x, bool is_msg, uint32_t tnode, uint32_t 
                                   prange_r.x, prange_r.y))
           return;
         if (wrote) LRS(me) = rsprev;
+        // a leader that takes entries from another leader of its term (MR_F_BUG_VOTE_TWICE) may
+        // now hold older entries above its base: from here it reads terms from the log
+        if (wrote && role == R_L) {
+          PR(PF_MATCH, me, me) = LBASE_NONE;
+          put_nb(pv.mt, me, LBASE_NONE);
+        }
         uint32_t lc = ma + k;
         if (mc < lc) lc = mc;
         if (lc > d.commit) d.commit = lc;
@@ -1623,6 +1631,10 @@ DI void node_event(const Dev& Darg, X& x, bool is_msg, uint32_t tnode, uint32_t 
           }
           d.snap = idx; d.snapt = mb; NSV(me) = MSV(slot);
           d.commit = idx; d.applied = idx;
+          if (role == R_L) {  // as a leader that takes entries (M_AE_REQ above)
+            PR(PF_MATCH, me, me) = LBASE_NONE;
+            put_nb(pv.mt, me, LBASE_NONE);
+          }
           adig_set(D, x.c, me, true);
           storage_snapshot(D, x, me, d.slen, idx);
           if (x.code != RUN) return;

@@ -14,45 +14,11 @@ import pytest
 
 from madraft_amd import _abi
 from tests.oracle_lib import COUNTER_KEYS
+from tests.parity_util import compare, first_diff, hist_of
 
 pytestmark = pytest.mark.gpu
 
 SUPPORTED = [n for n in _abi.SCENARIOS if n and n not in _abi.GPU_UNSUPPORTED]
-
-
-def first_diff(a, b):
-    n = min(len(a), len(b))
-    for i in range(n):
-        if a[i] != b[i]:
-            return i, a[i], b[i]
-    return n, (a[n] if n < len(a) else None), (b[n] if n < len(b) else None)
-
-
-def compare(hip, oracle, test, clusters, traced=4, first=0, oracle_codes=False, **kw):
-    with hip.Batch(test, clusters, trace_clusters=traced, cluster_base=first, **kw) as b:
-        st = b.run()
-        assert st["remaining"] == 0
-        code, t, dig = b.verdicts()
-        cnt = b.counters()
-        traces = [b.trace(k) for k in range(traced)]
-        tdigs = [b.trace_digests(k) for k in range(traced)]
-        cfg = b.cfg
-    ocode, ot, odig, osum = oracle.run_batch(cfg, 0, clusters)
-    for k in range(traced):
-        _, otr, odg = oracle.run_cluster_dig(cfg, k, int(cfg.trace_cap))
-        if not np.array_equal(traces[k], otr):
-            i, g, o = first_diff(traces[k], otr)
-            pytest.fail(f"{test} cluster {k}: trace differs at record {i}: gpu={g} oracle={o}")
-        if not np.array_equal(tdigs[k], odg):
-            i = int(np.nonzero(tdigs[k] != odg)[0][0])
-            pytest.fail(f"{test} cluster {k}: apply digest differs at record {i}: {traces[k][i]}")
-    bad = np.nonzero((code != ocode) | (t != ot) | (dig != odig))[0]
-    assert bad.size == 0, (f"{test}: {bad.size} clusters differ, first {bad[0]}: "
-                           f"gpu=({code[bad[0]]},{t[bad[0]]}) oracle=({ocode[bad[0]]},{ot[bad[0]]})")
-    for k in COUNTER_KEYS:
-        assert cnt[k] == osum[k], (test, k, cnt[k], osum[k])
-    assert cnt["done"] == clusters
-    return (code, cnt, ocode) if oracle_codes else (code, cnt)
 
 
 def golden_hist(name):
@@ -62,11 +28,6 @@ def golden_hist(name):
     import os
     gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "verdict_hist.json")))
     return next(c for c in gold["cases"] if c["name"] == name)
-
-
-def hist_of(code):
-    vals, cnt = np.unique(code, return_counts=True)
-    return {str(int(v)): int(n) for v, n in zip(vals, cnt)}
 
 
 @pytest.mark.parametrize("test", SUPPORTED)
