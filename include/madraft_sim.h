@@ -572,6 +572,41 @@ int mr_batch_set_seeds(mr_batch* b, const uint32_t* seed_cluster /* [n_clusters]
  * misses, off all 0. An error if out != NULL and cap < off[count]. */
 int mr_batch_get_decisions_packed(mr_batch* b, uint32_t first, uint32_t count, uint64_t* drawn,
                                   uint64_t* off, mr_decision* out, size_t cap);
+/* ---- parameter groups (an addition within ABI 7, docs/SEMANTICS.md §12.4) ----
+ * One batch sweeps the settings of the system under test: position c is in group group_of[c], and
+ * runs exactly what a batch created from cfg_g runs at that position's seed, where cfg_g is the
+ * batch's cfg with the group's non-zero numeric fields and with the sweepable flag bits
+ * (MR_F_SWEEPABLE) taken from the group's flags: they REPLACE cfg.flags' sweepable bits, so an
+ * all-zero group inherits the numbers and clears those bits. MR_F_SAFETY, MR_F_TRACE, MR_F_RECORD,
+ * MR_F_STREAM, n_nodes, every capacity and max_events stay the batch's: they size arrays or select
+ * kernels. The groups are the batch's, as a seed list is: they survive mr_batch_reset,
+ * mr_batch_submit and every set_decisions / set_variants* / set_seeds call; only n_groups == 0 here
+ * or mr_batch_destroy drops them. Call after create / reset and before run. While they are set the
+ * batch runs "step_kernel_tape"; they compose with every decision source (a seed list gives the
+ * paired design: the same seeds in every group; MR_F_RECORD records position c's tape under its
+ * group; replay and variants look draws up as before). Errors, each of which leaves the batch as it
+ * was: a group_of[c] >= n_groups, a flag bit outside MR_F_SWEEPABLE, non-zero reserved,
+ * elect_hi_us <= elect_lo_us after inheritance, ae_max > cfg.ae_max, a submitted step not yet
+ * finished. */
+#define MR_F_SWEEPABLE                                                                             \
+  (MR_F_UNRELIABLE | MR_F_NULL_RAFT | MR_F_BUG_VOTE_TWICE | MR_F_BUG_VOTE_STALE |                  \
+   MR_F_BUG_NO_PREV_CHECK | MR_F_BUG_NO_DEDUP | MR_F_BUG_STALE_READ | MR_F_BUG_NO_APPLY_CHECK)
+typedef struct mr_param_group {
+  uint32_t flags;        /* the group's MR_F_SWEEPABLE bits: they replace cfg.flags' */
+  uint32_t hb_us;        /* 0 = cfg's, likewise below */
+  uint32_t elect_lo_us, elect_hi_us;
+  uint32_t ae_max;       /* <= cfg.ae_max: payloads are sized and strided by the batch's */
+  uint32_t iters;
+  uint32_t reserved[2];  /* 0 */
+} mr_param_group;        /* 32 B */
+int mr_batch_set_param_groups(mr_batch* b, const mr_param_group* g, size_t n_groups,
+                              const uint32_t* group_of /* [n_clusters] */);
+/* mr_batch_counters restricted to the positions of one group, as of the batch's last run (one
+ * grouped reduce pass fills every group's row; this call copies one): sums, maxima, fail_hist, both
+ * coverage histograms, the service counters, clusters = the group's positions, and
+ * first_fail_cluster = its first failing position + cluster_base (UINT64_MAX: none). An error if
+ * `group` is out of range or no groups are set. */
+int mr_batch_group_counters(mr_batch* b, uint32_t group, mr_counters* out);
 /* One cluster of cfg (cluster_base selects the seed for misses) driven by the n decisions:
  * its per-event trace (per-node term / role / commit / applied / last / snapshot after every
  * event), its verdict and verdict time, and (misses != NULL) its draws not in `d`. */

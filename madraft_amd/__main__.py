@@ -5,7 +5,9 @@ analogue of `MADSIM_TEST_SEED=S MADSIM_TEST_NUM=N cargo test <test>`;
 1-minimal set of dropped (or delayed) messages (madraft_amd/shrink.py);
 `--clusters N --shrink-failures [K]` runs the N seeds and shrinks the first K failing ones in one
 variant batch of groups, one launch per ddmin round for all of them; `--seeds LIST` (or `@file`)
-runs exactly those seeds in one batch (docs/SEMANTICS.md §12.3), and with `--shrink` shrinks them."""
+runs exactly those seeds in one batch (docs/SEMANTICS.md §12.3), and with `--shrink` shrinks them;
+`--sweep FIELD=V1,V2,...` (repeatable) runs every combination of the settings over the same seeds
+in one batch of parameter groups (§12.4) and prints one JSON line per setting."""
 import argparse
 import json
 import time
@@ -48,7 +50,46 @@ def parse_seeds(arg):
     return seeds
 
 
-def main():
+SWEEP_FIELDS = ("hb_us", "ae_max", "iters", "elect_us", "bug")
+
+
+def parse_sweep(specs):
+    """`--sweep` arguments as run_sweep's grid, in the order given: "hb_us=25000,50000" (likewise
+    ae_max, iters), "elect_us=150000:300000,50000:60000" (lo:hi pairs), "bug=none,vote_stale"."""
+    grid = {}
+    for spec in specs:
+        field, eq, vals = spec.partition("=")
+        words = [w.strip() for w in vals.split(",") if w.strip()]
+        if not eq or field not in SWEEP_FIELDS or not words:
+            raise ValueError(f"--sweep {spec!r}: want FIELD=V1,V2,... with FIELD one of "
+                             f"{', '.join(SWEEP_FIELDS)}")
+        if field in grid:
+            raise ValueError(f"--sweep {spec!r}: {field} is swept twice")
+        if field == "bug":
+            bad = [w for w in words if w not in _abi.BUG_FLAGS]
+            if bad:
+                raise ValueError(f"--sweep {spec!r}: unknown bug {bad[0]!r}")
+            grid[field] = words
+        elif field == "elect_us":
+            pairs = [tuple(int(v, 0) for v in w.split(":")) for w in words]
+            if any(len(p) != 2 or p[1] <= p[0] for p in pairs):
+                raise ValueError(f"--sweep {spec!r}: want lo:hi pairs with lo < hi")
+            grid[field] = pairs
+        else:
+            grid[field] = [int(w, 0) for w in words]
+    return grid
+
+
+def sweep_line(r):
+    """One setting of a sweep as the command line reports it."""
+    cnt = r["counters"]
+    failing = (r["codes"] != _abi.MR_PASS).nonzero()[0]
+    return {"params": r["params"], "passed": cnt["passed"], "failed": cnt["failed"],
+            "fail_hist": cnt["fail_hist"],  # (the non-zero verdict counts by name, PASS among them)
+            "first_fail_seed": r["seeds"][int(failing[0])] if failing.size else None}
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("test")
     ap.add_argument("--clusters", type=int, default=None, help="seeds (MADSIM_TEST_NUM)")
@@ -75,7 +116,19 @@ def main():
                     help="run the --clusters seeds from --seed and shrink the first K failing "
                          "ones together (default 16; 0 = all), one JSON line per seed in --shrink's "
                          "format and a summary line")
-    a = ap.parse_args()
+    ap.add_argument("--sweep", action="append", default=[], metavar="FIELD=V1,V2,...",
+                    help="sweep a setting over the same seeds in one batch (repeatable: every "
+                         "combination): hb_us, ae_max, iters, elect_us=lo:hi,..., bug=none,NAME,...")
+    a = ap.parse_args(argv)
+    grid = None
+    if a.sweep:
+        if a.replay or a.shrink or a.shrink_failures is not None:
+            ap.error("--sweep does not go with --replay, --shrink or --shrink-failures: shrink a "
+                     "failing (seed, setting) by passing that setting batch-wide")
+        try:
+            grid = parse_sweep(a.sweep)
+        except ValueError as e:
+            ap.error(str(e))
     flags = 0
     if a.bug:
         flags |= {"vote_twice": _abi.MR_F_BUG_VOTE_TWICE, "vote_stale": _abi.MR_F_BUG_VOTE_STALE,
@@ -133,6 +186,13 @@ def main():
                               "launches": res.launches,
                               "kept_sizes": sorted({int(r.kept.size) for r in done})}))
         raise SystemExit(0)
+    if grid:
+        seeds = a.seeds or [(_abi.README_SEED if a.seed is None else a.seed) + k
+                            for k in range(a.clusters or 1)]
+        res = sim.run_sweep(a.test, grid, seeds=seeds, **cfg_kw)
+        for r in res:
+            print(json.dumps(sweep_line(r)))
+        raise SystemExit(1 if any(r["counters"]["failed"] for r in res) else 0)
     t0 = time.time()
     if a.seeds:
         code, _, _, cnt = sim.run_seeds(a.test, a.seeds, **cfg_kw)

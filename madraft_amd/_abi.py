@@ -162,6 +162,18 @@ LOSS_Q32 = 429496729  # floor(0.1 * 2^32), tester.rs:130
 VARIANT_GROUP_DTYPE = np.dtype([("seed_cluster", "<u4"), ("base_off", "<u4"), ("n_base", "<u4"),
                                 ("edit_off", "<u4"), ("n_edits", "<u4")])
 assert VARIANT_GROUP_DTYPE.itemsize == 20
+# mr_param_group (parameter groups, docs/SEMANTICS.md §12.4): one setting of a sweep; 0 = the batch's
+PARAM_GROUP_DTYPE = np.dtype([("flags", "<u4"), ("hb_us", "<u4"), ("elect_lo_us", "<u4"),
+                              ("elect_hi_us", "<u4"), ("ae_max", "<u4"), ("iters", "<u4"),
+                              ("reserved", "<u4", (2,))])
+assert PARAM_GROUP_DTYPE.itemsize == 32
+# MR_F_SWEEPABLE: the flag bits a group sets for its positions (they replace the batch's)
+SWEEPABLE_FLAGS = (MR_F_UNRELIABLE | MR_F_NULL_RAFT | MR_F_BUG_VOTE_TWICE | MR_F_BUG_VOTE_STALE |
+                   MR_F_BUG_NO_PREV_CHECK | MR_F_BUG_NO_DEDUP | MR_F_BUG_STALE_READ |
+                   MR_F_BUG_NO_APPLY_CHECK)
+# the buggy Raft variants by the names the command line takes (--bug, --sweep bug=)
+BUG_FLAGS = {"none": 0, "vote_twice": MR_F_BUG_VOTE_TWICE, "vote_stale": MR_F_BUG_VOTE_STALE,
+             "no_prev_check": MR_F_BUG_NO_PREV_CHECK}
 
 
 def decision_word(v, lo, hi):
@@ -185,4 +197,5 @@ EXPORTS = [
     "mr_batch_set_variants", "mr_batch_set_variant_masks",  # ABI 5
     "mr_batch_set_variant_groups",  # ABI 6
     "mr_batch_set_seeds", "mr_batch_get_decisions_packed",  # ABI 7
+    "mr_batch_set_param_groups", "mr_batch_group_counters",  # parameter groups (within ABI 7)
 ]

@@ -259,7 +259,16 @@ struct Dev {
   uint32_t gprobe;  // MR_GUARD builds, MR_GUARD_PROBE set: cluster 0's first delivery reads slot M
   unsigned long long* pcnt;  // pool_kernel: the workgroups' counter sums (64-bit; reduce adds them)
   uint32_t krows;   // the 7-server Raft pool: message slots whose keys live in LDS (the rest in HBM)
+  // parameter groups (mr_batch_set_param_groups, SEMANTICS §12.4), else null: [C] one PG_W-word
+  // record per cluster, its group's values of the eight parameters above that a group may set
+  // (PG_*; one load, no group_of -> groups indirection, as tdesc). Read by the tape kernels'
+  // accessors only (mr_kernel.hip p_hb() ..); the batch's own allocation beside sof, no row of
+  // MR_DEV_ARRAYS. Last, so that no field the step and pool kernels read moves
+  const uint32_t* pgrp;
 };
+// a cluster's parameter record (Dev::pgrp): the group's value of Dev's field of the same name
+enum : uint32_t { PG_HB, PG_ELO, PG_EHI, PG_K, PG_ITERS, PG_BUGS, PG_UNREL, PG_NULL, PG_W };
+static_assert(PG_W * 4 == sizeof(mr_param_group), "one 32-B record per cluster");
 // words-pairs per cluster of kwk: the thread slots rounded up to whole 16-B quads (two slots each;
 // slot 0 = the test body and the pad slot hold ~0, so they never win a rescan)
 constexpr uint32_t kws(uint32_t nthr) { return (nthr + 1u) & ~1u; }

@@ -92,6 +92,8 @@ static bool use_pool(uint32_t scn, uint32_t n, uint32_t M) {
 hipError_t launch_reset(const Dev& D, hipStream_t s);
 hipError_t launch_reduce(const Dev& D, unsigned long long* out, uint64_t cluster_base,
                          hipStream_t s);
+hipError_t launch_group_reduce(const Dev& D, const uint32_t* gof, uint32_t n_groups,
+                               unsigned long long* out, uint64_t cluster_base, hipStream_t s);
 hipError_t launch_tape_pack(const uint4* tape, const uint32_t* used, uint32_t dcap, uint32_t first,
                             uint32_t count, const uint64_t* off, uint32_t* out, hipStream_t s);
 }  // namespace mr
@@ -164,6 +166,17 @@ struct Tables {
   Owner mode = OWN_NONE;
 };
 
+// A batch's parameter groups on the device (mr_batch_set_param_groups), each array its own
+// allocation, staged whole and moved in as one. All null: every cluster runs the batch's cfg.
+struct ParamGroups {
+  DevMem<uint32_t> rec;             // [C][PG_W] the clusters' parameter records (Dev::pgrp)
+  DevMem<uint32_t> gof;             // [C] the clusters' groups, for the grouped reduce
+  DevMem<unsigned long long> red;   // [n][RED_N] the groups' reduce rows (group_reduce_kernel)
+  std::vector<uint64_t> positions;  // [n] clusters of each group
+  bool fresh = false;               // red holds the reduce of the clusters as they stand
+  size_t n() const { return positions.size(); }
+};
+
 // the HBM format of a run's message keys: the pool kernel's (32-bit, AppendEntries bit), or the one
 // the step and tape kernels share
 enum KeyFormat : uint32_t { KEYS_UNSET, KEYS_POOL, KEYS_STEP };
@@ -194,6 +207,7 @@ struct mr_batch {
   uint32_t budget = 16384;       // events per cluster per launch (MR_STEP_BUDGET)
   Tables dec;                    // the decision tables D draws from (install_tables)
   DevMem<uint32_t> sof;          // the seed list (mr_batch_set_seeds): the batch's, not its tables'
+  ParamGroups pg;                // the parameter groups (mr_batch_set_param_groups): the batch's too
   RunState run;
 };
 struct BatchDestroy {
@@ -213,10 +227,12 @@ static int copy_trace_row(mr_batch* b, uint32_t k, const T* rows, T* out, size_t
   return 0;
 }
 
-// Dev's tape_mode: what a draw does with the owner's tables, or with a seed list and no tables
+// Dev's tape_mode: what a draw does with the owner's tables, or without tables on a batch that
+// needs the tape kernels all the same: for a seed list, or for parameter groups (TAPE_SEEDS with a
+// null list is Philox from the cluster's own seed)
 static TapeMode tape_mode_of(const mr_batch* b) {
   if (b->dec.mode == OWN_RECORD) return TAPE_RECORD;
-  return b->dec.mode != OWN_NONE ? TAPE_LOOKUP : b->sof ? TAPE_SEEDS : TAPE_OFF;
+  return b->dec.mode != OWN_NONE ? TAPE_LOOKUP : b->sof || b->pg.rec ? TAPE_SEEDS : TAPE_OFF;
 }
 
 // `t` (staged whole by the caller) becomes the batch's decision tables, the previous ones are
@@ -243,6 +259,9 @@ static int no_throw(const char* name, Fn fn) {
 }
 
 extern "C" {
+
+static int group_reduce(mr_batch* b);
+static int fill_counters(mr_batch* b, const unsigned long long* h, uint64_t clusters, mr_counters* out);
 
 const char* mr_last_error(void) { return g_err.c_str(); }
 
@@ -392,6 +411,7 @@ static int mr_batch_create_impl(const mr_cfg* cfg, mr_batch** out) {
 static int enqueue_reset(mr_batch* b, uint64_t seed_base) {
   b->cfg.seed_base = seed_base;
   b->run = RunState{};
+  b->pg.fresh = false;
   b->D.seed0 = seed_base + b->cfg.cluster_base;
   HIPCHK(hipSetDevice(b->cfg.device));
   for (int k = 0; k < (int)A__N; k++)  // the table's ZERO rows this batch has, by their place k
@@ -508,6 +528,7 @@ static int run_from(mr_batch* b, uint64_t max_events, std::chrono::steady_clock:
   if (rc != 0 || guard_check(b) != 0) return -1;
   mr_counters c;
   if (mr_batch_counters(b, &c) != 0) return -1;
+  if (b->pg.rec && group_reduce(b) != 0) return -1;  // every group's row, one pass
   s.events = c.events;
   s.remaining = c.clusters - c.done;
   s.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -574,8 +595,26 @@ int mr_batch_counters(mr_batch* b, mr_counters* out) {
   HIPCHK(launch_reduce(b->D, b->red.get(), b->cfg.cluster_base, b->stream.get()));
   HIPCHK(hipMemcpyAsync(h.data(), b->red.get(), RED_N * 8, hipMemcpyDeviceToHost, b->stream.get()));
   HIPCHK(hipStreamSynchronize(b->stream.get()));
+  return fill_counters(b, h.data(), b->D.C, out);
+}
+
+// the parameter groups' reduce rows as of now: preset, one group_reduce_kernel pass, on the stream
+static int group_reduce(mr_batch* b) {
+  ParamGroups& pg = b->pg;
+  std::vector<unsigned long long> h(pg.n() * RED_N, 0);
+  for (size_t g = 0; g < pg.n(); g++) h[g * RED_N + RED_FIRST_FAIL] = ~0ull;
+  HIPCHK(hipMemcpyAsync(pg.red.get(), h.data(), h.size() * 8, hipMemcpyHostToDevice, b->stream.get()));
+  HIPCHK(launch_group_reduce(b->D, pg.gof.get(), (uint32_t)pg.n(), pg.red.get(), b->cfg.cluster_base,
+                             b->stream.get()));
+  HIPCHK(hipStreamSynchronize(b->stream.get()));  // (h is read until the copy is done)
+  pg.fresh = true;
+  return 0;
+}
+
+// mr_counters of `clusters` clusters from a reduce vector h[RED_N] (mr_dev.h CNT_* and RED_*)
+static int fill_counters(mr_batch* b, const unsigned long long* h, uint64_t clusters, mr_counters* out) {
   std::memset(out, 0, sizeof *out);
-  out->clusters = b->D.C;
+  out->clusters = clusters;
 #define MR_ROW_(sym, field, red, who) out->field = h[CNT_##sym];
   MR_COUNTER_TABLE(MR_ROW_)
 #undef MR_ROW_
@@ -988,6 +1027,80 @@ int mr_batch_set_seeds(mr_batch* b, const uint32_t* seed_cluster) {
   b->D.sof = b->sof.get();
   b->D.tape_mode = tape_mode_of(b);
   return 0;
+}
+
+// The batch's parameter groups (madraft_sim.h): every group resolved against the batch's cfg and
+// checked, every position's group checked, then one 32-B record per cluster (its group's values, as
+// the kernels' accessors read them), the clusters' groups and the groups' reduce rows staged whole
+// before the previous groups are freed by the move, so a rejected call leaves the batch as it was.
+static int set_param_groups_impl(mr_batch* b, const mr_param_group* g, size_t n_groups,
+                                 const uint32_t* group_of) {
+  const size_t C = b->D.C;
+  const mr_cfg& cfg = b->cfg;
+  if (n_groups >= (1ull << 32)) return set_err("too many parameter groups (2^32 - 1 at most)");
+  std::vector<uint32_t> val(n_groups * PG_W);
+  for (size_t i = 0; i < n_groups; i++) {
+    const mr_param_group& G = g[i];
+    const std::string at = " (parameter group " + std::to_string(i) + ")";
+    if (G.flags & ~MR_F_SWEEPABLE) return set_err("a flag bit outside MR_F_SWEEPABLE" + at);
+    if (G.reserved[0] || G.reserved[1]) return set_err("reserved words must be 0" + at);
+    uint32_t* v = val.data() + i * PG_W;
+    v[PG_HB] = G.hb_us ? G.hb_us : cfg.hb_us;
+    v[PG_ELO] = G.elect_lo_us ? G.elect_lo_us : cfg.elect_lo_us;
+    v[PG_EHI] = G.elect_hi_us ? G.elect_hi_us : cfg.elect_hi_us;
+    v[PG_K] = G.ae_max ? G.ae_max : cfg.ae_max;
+    v[PG_ITERS] = G.iters ? G.iters : b->D.iters;  // (the batch's: cfg's, or the test body's own)
+    v[PG_BUGS] = G.flags & MR_F_SWEEPABLE & ~(MR_F_UNRELIABLE | MR_F_NULL_RAFT);
+    v[PG_UNREL] = (G.flags & MR_F_UNRELIABLE) ? 1u : 0u;
+    v[PG_NULL] = (G.flags & MR_F_NULL_RAFT) ? 1u : 0u;
+    if (v[PG_EHI] <= v[PG_ELO]) return set_err("elect_hi_us <= elect_lo_us" + at);
+    if (v[PG_K] > cfg.ae_max) return set_err("ae_max above the batch's" + at);
+  }
+  ParamGroups pg;
+  pg.positions.assign(n_groups, 0);
+  std::vector<uint32_t> rec(C * PG_W);
+  for (size_t c = 0; c < C; c++) {
+    if (group_of[c] >= n_groups)
+      return set_err("group_of[" + std::to_string(c) + "] = " + std::to_string(group_of[c]) +
+                     ": no such parameter group");
+    pg.positions[group_of[c]]++;
+    std::memcpy(rec.data() + c * PG_W, val.data() + (size_t)group_of[c] * PG_W, PG_W * sizeof(uint32_t));
+  }
+  hipError_t e = upload(pg.rec, rec.data(), rec.size());
+  if (e == hipSuccess) e = upload(pg.gof, group_of, C);
+  if (e == hipSuccess) e = dev_alloc(pg.red, n_groups * RED_N);
+  if (e != hipSuccess)  // (pg goes, the batch keeps its previous groups)
+    return set_err(std::string("parameter groups: ") + hipGetErrorString(e));
+  b->pg = std::move(pg);
+  return 0;
+}
+
+int mr_batch_set_param_groups(mr_batch* b, const mr_param_group* g, size_t n_groups,
+                              const uint32_t* group_of) {
+  if (!b) return set_err("null batch");
+  if (n_groups && (!g || !group_of)) return set_err("null parameter groups");
+  if (b->run.submitted) return set_err("batch has a submitted step: mr_batch_finish it first");
+  HIPCHK(hipSetDevice(b->cfg.device));
+  HIPCHK(hipStreamSynchronize(b->stream.get()));
+  if (!n_groups) b->pg = ParamGroups{};
+  else if (const int rc = no_throw("parameter groups", [&] { return set_param_groups_impl(b, g, n_groups, group_of); }))
+    return rc;
+  b->D.pgrp = b->pg.rec.get();
+  b->D.tape_mode = tape_mode_of(b);
+  return 0;
+}
+
+int mr_batch_group_counters(mr_batch* b, uint32_t group, mr_counters* out) {
+  if (!b || !out) return set_err("null argument");
+  if (!b->pg.rec) return set_err("mr_batch_group_counters without parameter groups");
+  if (group >= b->pg.n())
+    return set_err("parameter group " + std::to_string(group) + " of " + std::to_string(b->pg.n()));
+  if (b->run.submitted) return set_err("batch has a submitted step: mr_batch_finish it first");
+  HIPCHK(hipSetDevice(b->cfg.device));
+  if (!b->pg.fresh && group_reduce(b) != 0) return -1;
+  unsigned long long h[RED_N];
+  HIPCHK(hipMemcpy(h, b->pg.red.get() + (size_t)group * RED_N, sizeof h, hipMemcpyDeviceToHost));
+  return fill_counters(b, h, b->pg.positions[group], out);
 }
 
 int mr_replay(const mr_cfg* cfg, const mr_decision* d, size_t n, mr_event* out, size_t cap,

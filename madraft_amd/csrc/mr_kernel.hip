@@ -120,6 +120,36 @@ __device__ __noinline__ uint32_t guard_bad(uint32_t* g, uint32_t tag, uint32_t c
 #define MSV(s) (*reinterpret_cast<uint64_t*>(MSP(s) + MF_V))
 #define MKEY(s) D.mkey[(size_t)GI(s, D.M, G_MSG) * D.C + x.c]
 #define TMR(d) D.tmr[(size_t)GI(d, D.n, G_NODE) * D.C + x.c]
+// The eight parameters a group may set (SEMANTICS §12.4; mr_dev.h PG_*), one accessor each. In the
+// decision-tape units a cluster reads its group's value while groups are set: a wave-uniform branch
+// on D.pgrp, then one per-lane load from the cluster's own 32-B record, issued at the use, so no
+// register holds a parameter across events. The value is per lane there: nothing
+// that takes it may assume a wave agrees on it. Every other unit reads D's wave-uniform scalar, and
+// its code is what it was. (D.K as the stride of `pay` is the batch's and is read as D.K.)
+#if MR_TAPE
+#define MR_PARAM_(name, field, pg)                                               \
+  DI uint32_t name(const Dev& D, const X& x) {                                   \
+    return D.pgrp ? D.pgrp[(size_t)x.c * PG_W + pg] : D.field;                   \
+  }
+MR_PARAM_(p_hb, hb, PG_HB)
+MR_PARAM_(p_elo, elo, PG_ELO)
+MR_PARAM_(p_ehi, ehi, PG_EHI)
+MR_PARAM_(p_ae_max, K, PG_K)
+MR_PARAM_(p_iters, iters, PG_ITERS)
+MR_PARAM_(p_bugs, bugs, PG_BUGS)
+MR_PARAM_(p_unrel, unrel_flag, PG_UNREL)
+MR_PARAM_(p_null_raft, null_raft, PG_NULL)
+#undef MR_PARAM_
+#else  // (the field itself, token for token what these units read before: their code objects stay)
+#define p_hb(D, x) ((D).hb)
+#define p_elo(D, x) ((D).elo)
+#define p_ehi(D, x) ((D).ehi)
+#define p_ae_max(D, x) ((D).K)
+#define p_iters(D, x) ((D).iters)
+#define p_bugs(D, x) ((D).bugs)
+#define p_unrel(D, x) ((D).unrel_flag)
+#define p_null_raft(D, x) ((D).null_raft)
+#endif
 // message keys of the lane's cluster live in LDS during a launch: [slot][lane],
 // so a wave's 64 lanes read 64 consecutive u64 (conflict-free). Free slots hold
 // ~0, so the earliest-message scan is a branch-free min over all M slots.
@@ -522,7 +552,7 @@ DI void fail(const Dev& D, X& x, uint32_t code) {
 DI void reset_timer(const Dev& D, X& x, uint32_t d, NC& n) {  // raft.rs:260-263
   uint32_t w0, w1;
   philox(D, x, n.ectr++, d, ST_ELECT, w0, w1);
-  set_timer(x, d, x.now + u_range(w0, D.elo, D.ehi));
+  set_timer(x, d, x.now + u_range(w0, p_elo(D, x), p_ehi(D, x)));
 }
 
 // the earliest-message rescan four occupied slots per trip, their LDS reads issued together:
@@ -860,6 +890,7 @@ DI Dev dev_launder(const Dev& D0) {
     D.tdesc = glp(D0.tdesc); D.vedit = glp(D0.vedit); D.vwords = glp(D0.vwords);
     D.vmask = glp(D0.vmask);
     D.sof = glp(D0.sof);  // a seed list (null otherwise)
+    D.pgrp = glp(D0.pgrp);  // the clusters' parameter records (null otherwise)
   }
   return D;
 }
@@ -907,7 +938,7 @@ DI void node_apply(const Dev& D, X& x, uint32_t me, NC& d, uint32_t& kvready, ui
       d.applied = i;
       if (i >= D.apply_cap) { fail(D, x, MR_FAIL_SIM_CAPACITY); return; }
       CADD(CNT_APPLIES, 1u);
-      if (cm[j] && csv[j] != ce[j].val && !(D.bugs & MR_F_BUG_NO_APPLY_CHECK)) {  // tester.rs:384
+      if (cm[j] && csv[j] != ce[j].val && !(p_bugs(D, x) & MR_F_BUG_NO_APPLY_CHECK)) {  // tester.rs:384
         fail(D, x, MR_FAIL_APPLY_MISMATCH);
         return;
       }
@@ -1027,7 +1058,7 @@ DI void node_apply_coop(const Dev& D, X& x, uint32_t me, NC& d) {
     uint32_t key = ~0u;
     if (mine) {
       if (!inb) key = (i << 2) | 0u;                                    // SIM_CAPACITY
-      else if (s.mask && s.val != e.val && !(D.bugs & MR_F_BUG_NO_APPLY_CHECK))
+      else if (s.mask && s.val != e.val && !(p_bugs(D, x) & MR_F_BUG_NO_APPLY_CHECK))
         key = (i << 2) | 1u;                                            // APPLY_MISMATCH
       else if (i == obase && obase > olen) key = (i << 2) | 2u;         // APPLY_OUT_OF_ORDER
     }
@@ -1480,8 +1511,8 @@ DI void node_event(const Dev& Darg, X& x, bool is_msg, uint32_t tnode, uint32_t 
         const uint32_t lt = d.lastt;  // term_at(last)
         bool up = (mc > lt) || (mc == lt && mb >= d.last);
         uint32_t voted = f_voted(d.f);
-        if (D.bugs & MR_F_BUG_VOTE_STALE) up = true;
-        const bool free_vote = voted == 15u || voted == ma || (D.bugs & MR_F_BUG_VOTE_TWICE);
+        if (p_bugs(D, x) & MR_F_BUG_VOTE_STALE) up = true;
+        const bool free_vote = voted == 15u || voted == ma || (p_bugs(D, x) & MR_F_BUG_VOTE_TWICE);
         bool granted = (mterm == term) && free_vote && up;
         if (granted) {
           d.f = f_set(d.f, 4, 4, ma);
@@ -1509,7 +1540,7 @@ DI void node_event(const Dev& Darg, X& x, bool is_msg, uint32_t tnode, uint32_t 
               PR(PF_NEXT, me, p) = pv.nx[p];
               PR(PF_MATCH, me, p) = pv.mt[p];
             }
-            set_timer(x, me, x.now + D.hb);
+            set_timer(x, me, x.now + p_hb(D, x));
             mode = SEND_APPEND; peers = others;
           }
         }
@@ -1539,7 +1570,7 @@ DI void node_event(const Dev& Darg, X& x, bool is_msg, uint32_t tnode, uint32_t 
         le_at(D, x, me, d, lrs, prev, tp, rsp);
         ae_load_batch(D, x, me, d, src, mat, pp, ma, k, j0, pe, lt, ov, ors);
         PROF(P_AE_PROBE);
-        if (!(D.bugs & MR_F_BUG_NO_PREV_CHECK) && tp != pterm) {
+        if (!(p_bugs(D, x) & MR_F_BUG_NO_PREV_CHECK) && tp != pterm) {
           rb = prev <= d.snap ? prev : (rsp > d.snap + 1u ? rsp : d.snap + 1u);
           break;
         }
@@ -1657,7 +1688,7 @@ DI void node_event(const Dev& Darg, X& x, bool is_msg, uint32_t tnode, uint32_t 
     }
   } else if (f_role(d.f) == R_L) {  // heartbeat / replication round
     kind = 1;
-    set_timer(x, me, x.now + D.hb);
+    set_timer(x, me, x.now + p_hb(D, x));
     mode = SEND_APPEND; peers = others;
     PROF(P_HB);
   } else {  // election timeout: become candidate
@@ -1766,7 +1797,7 @@ DI void node_event(const Dev& Darg, X& x, bool is_msg, uint32_t tnode, uint32_t 
       } else {
         prev = nx - 1;
         sk = d.last - prev;
-        if (sk > D.K) sk = D.K;
+        if (sk > p_ae_max(D, x)) sk = p_ae_max(D, x);
         st = M_AE_REQ; sa = prev; sb = LPT(p); sc = d.commit;
       }
     }
@@ -1830,13 +1861,13 @@ DI void t_start1(const Dev& D, X& x, uint32_t i) {  // tester.rs:293-327, raft.r
   n.commit = n.snap;
   n.applied = n.snap;
   adig_set(D, x.c, i, n.snap != 0u);
-  if (!D.null_raft) reset_timer(D, x, i, n);
+  if (!p_null_raft(D, x)) reset_timer(D, x, i, n);
   store_node(D, x, i, n);
 }
 DI void t_new(const Dev& D, X& x, bool snapshot) {  // RaftTester::new, tester.rs:34-60
   x.netmode = (x.netmode & ~2u) | (snapshot ? 2u : 0u);
   for (uint32_t i = 0; i < D.n; i++) { t_start1(D, x, i); t_conn(D, x, i, 1); }
-  if (D.unrel_flag) t_set_unrel(x, true);
+  if (p_unrel(D, x)) t_set_unrel(x, true);
 }
 // bit mask of the servers whose role is leader: x.lmask, kept by store_node (every role change
 // of a record passes there), so is_leader() sampling reads no record
@@ -1846,7 +1877,7 @@ DI uint32_t t_leaders(const Dev& D, X& x) { return x.lmask; }
 DI bool t_start(const Dev& D, X& x, uint32_t i, uint64_t v, uint32_t& idx, uint32_t& term,
                 bool lead) {
   if (!bit(x.alive, i)) { fail(D, x, MR_FAIL_UNWRAP_NONE); return false; }
-  if (D.null_raft || !lead) return false;  // Err(NotLeader((me+1)%n))
+  if (p_null_raft(D, x) || !lead) return false;  // Err(NotLeader((me+1)%n))
   // words 0..15 of the record (scalars, pending payload range) and rs(last) as one batch of
   // independent loads: the write guard below needs no further round trip
   const uint4* rp = reinterpret_cast<const uint4*>(NDP(i));
@@ -1876,7 +1907,7 @@ DI bool t_start(const Dev& D, X& x, uint32_t i, uint64_t v, uint32_t& idx, uint3
 DI uint64_t t_entry_for_start(const Dev& D, X& x, uint32_t i, uint32_t lm);
 DI void t_start_burst(const Dev& D, X& x, uint32_t i, uint32_t count) {
   const uint32_t lm = t_leaders(D, x);
-  const bool go = bit(x.alive, i) && !D.null_raft && bit(lm, i);
+  const bool go = bit(x.alive, i) && !p_null_raft(D, x) && bit(lm, i);
   uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0, r2 = r0;
   uint2 pr = make_uint2(0u, 0u);
   uint32_t lrs = 0;
@@ -1962,7 +1993,7 @@ DI void t_check_no_leader(const Dev& D, X& x) {  // tester.rs:112-122
   for (uint32_t i = 0; i < D.n; i++) {
     if (!bit(x.conn, i)) continue;
     if (!bit(x.alive, i)) { fail(D, x, MR_FAIL_UNWRAP_NONE); return; }
-    if (!D.null_raft && bit(t_leaders(D, x), i)) {
+    if (!p_null_raft(D, x) && bit(t_leaders(D, x), i)) {
       fail(D, x, MR_FAIL_UNEXPECTED_LEADER);
       return;
     }
@@ -2441,6 +2472,89 @@ __global__ void __launch_bounds__(256) reduce_kernel(Dev D, unsigned long long* 
     if (cnt_is_max(i) && i < CNT__N) atomicMax(&out[i], acc[i]);
     else atomicAdd(&out[i], acc[i]);
   }
+}
+
+// One cluster's contribution to a reduce vector as reduce_kernel forms it (mr_dev.h CNT_* and RED_*),
+// for the grouped reduce: put(slot, value) for every slot but RED_FIRST_FAIL, which the caller
+// derives from the returned verdict code. A CNT slot that cnt_is_max names reduces as a maximum,
+// every other slot as a sum (red_is_max)
+constexpr bool red_is_max(uint32_t slot) { return slot < CNT__N && cnt_is_max(slot); }
+template <class Put>
+DI uint32_t red_cluster(const Dev& D, const X& x, Put put) {
+  for (uint32_t k = 0; k < CNT__N; k++) put(k, (unsigned long long)CS(CS_CNT + k));
+  const uint32_t code = CS(CS_CODE);
+  put(RED_EVENTS, (unsigned long long)CS(CS_EVENTS));
+  put(RED_MSGS, (unsigned long long)CS(CS_MSGS));
+  put(RED_VTIME, (unsigned long long)CS(CS_VTIME));
+  put(RED_DONE, code != RUN ? 1ull : 0ull);
+  put(RED_PASSED, code == MR_PASS ? 1ull : 0ull);
+  if (code != RUN) put(RED_FAIL_HIST + (code < 63 ? code : 63), 1ull);
+  auto bucket = [](uint32_t v) { return v == 0 ? 0u : min(15u, 32u - (uint32_t)__builtin_clz(v)); };
+  put(RED_COV_LEADERS + bucket(CS(CS_CNT + CNT_LEADERS)), 1ull);
+  put(RED_COV_EVENTS + bucket(CS(CS_EVENTS)), 1ull);
+  put(RED_KV_OPS, (unsigned long long)CS(CS_KV_OPS));
+  put(RED_KV_CHECKED, (unsigned long long)CS(CS_KV_CHECKED));
+  put(RED_KV_LIN, (unsigned long long)CS(CS_KV_LIN));
+  return code;
+}
+// row[slot] takes v by the slot's rule, atomically (row: a workgroup's LDS partial or an output row)
+DI void red_put(unsigned long long* row, uint32_t slot, unsigned long long v) {
+  if (red_is_max(slot)) atomicMax(&row[slot], v);
+  else atomicAdd(&row[slot], v);
+}
+
+// mr_batch_group_counters (SEMANTICS §12.4): reduce_kernel per parameter group, every group in one
+// pass over the per-cluster rows. out is [n_groups][RED_N] with reduce_kernel's slots and rules, its
+// RED_FIRST_FAIL slots preset to ~0 and the rest to 0; gof[c] < n_groups is cluster c's group (the
+// host checked it). Thread t of a block reads cluster 256 b + t of every cluster-minor row, so a
+// wave reads 64 consecutive words per field. Partials of the groups below GR_LDS accumulate in the
+// workgroup's LDS rows (64-bit LDS atomics: sum, max, and min for the first-fail key) and merge
+// into out with one 64-bit global atomic per non-empty slot; a cluster of a later group (a sweep of
+// more than GR_LDS settings) adds to its output row directly.
+constexpr uint32_t GR_LDS = 32, GR_BLOCK = 256;
+__global__ void __launch_bounds__(GR_BLOCK) group_reduce_kernel(Dev D, const uint32_t* gof,
+                                                                uint32_t n_groups,
+                                                                unsigned long long* out,
+                                                                uint64_t cluster_base) {
+  __shared__ unsigned long long acc[GR_LDS * RED_N];
+  const uint32_t held = (n_groups < GR_LDS ? n_groups : GR_LDS) * RED_N;  // the LDS rows in use
+  for (uint32_t i = threadIdx.x; i < held; i += GR_BLOCK) acc[i] = i % RED_N == RED_FIRST_FAIL ? ~0ull : 0ull;
+  __syncthreads();
+  X x;
+  x.c = blockIdx.x * GR_BLOCK + threadIdx.x;
+  if (x.c < D.C) {
+    const uint32_t g = gof[x.c];
+    const unsigned long long pos = cluster_base + x.c;
+    if (g < GR_LDS) {
+      unsigned long long* row = acc + g * RED_N;
+      const uint32_t code = red_cluster(D, x, [&](uint32_t i, unsigned long long v) {
+        if (v) red_put(row, i, v);
+      });
+      if (code != RUN && code != MR_PASS) atomicMin(&row[RED_FIRST_FAIL], pos);
+    } else {
+      unsigned long long* row = out + (size_t)g * RED_N;
+      const uint32_t code = red_cluster(D, x, [&](uint32_t i, unsigned long long v) {
+        if (v) red_put(row, i, v);
+      });
+      if (code != RUN && code != MR_PASS) atomicMin(&row[RED_FIRST_FAIL], pos);
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < held; i += GR_BLOCK) {
+    const uint32_t slot = i % RED_N;
+    const unsigned long long v = acc[i];
+    if (slot == RED_FIRST_FAIL) {
+      if (v != ~0ull) atomicMin(&out[i], v);
+    } else if (v) {  // (the two unused slots stay 0)
+      red_put(out + (i - slot), slot, v);
+    }
+  }
+}
+hipError_t launch_group_reduce(const Dev& D, const uint32_t* gof, uint32_t n_groups,
+                               unsigned long long* out, uint64_t cluster_base, hipStream_t s) {
+  dim3 blk(GR_BLOCK), grd((D.C + GR_BLOCK - 1) / GR_BLOCK);
+  hipLaunchKernelGGL(group_reduce_kernel, grd, blk, 0, s, D, gof, n_groups, out, cluster_base);
+  return hipGetLastError();
 }
 
 // mr_batch_get_decisions_packed: the used prefixes of the record tape's rows ([C][dcap] 16-B

@@ -242,7 +242,7 @@ DI void clerk_begin(const Dev& D, X& x, uint32_t slot, uint32_t op, uint32_t key
 DI bool clerk_resume(const Dev& D, X& x, uint32_t slot, KCR kc = KCR{}) {
   KS(KT_WAITING, 0u);
   // as shipped, ClerkCore::call is todo!() once call_timeout returns (kvraft/client.rs:59)
-  if (D.null_raft) { fail(D, x, MR_FAIL_TODO_RPC_RESULTS); return false; }
+  if (p_null_raft(D, x)) { fail(D, x, MR_FAIL_TODO_RPC_RESULTS); return false; }
   uint32_t lh = KR(KT_LH);
   if (KR(KT_GOT)) {
     const uint32_t st = KR(KT_RSTAT);
@@ -311,12 +311,12 @@ DI uint32_t kv_lin15_state(const uint32_t* kr, uint32_t a) {
 // KV_REQ at server me (server.rs:48-56 handler): reject, or start() and wait for the apply
 DI void kv_request(const Dev& D, X& x, uint32_t me, NC& d, uint32_t src, uint32_t clerk,
                    uint32_t tag, uint32_t opkey, uint32_t seq, uint32_t elem, uint2 prange) {
-  if (D.null_raft) { fail(D, x, MR_FAIL_TODO_APPLY); return; }  // as shipped: kvraft/server.rs:69
+  if (p_null_raft(D, x)) { fail(D, x, MR_FAIL_TODO_APPLY); return; }  // as shipped: kvraft/server.rs:69
   if (f_role(d.f) != R_L) {
     kv_send_rep(D, x, me, d, src, clerk, tag, KV_WRONG_LEADER, (me + 1u) % D.n, 0u, 0ull);
     return;
   }
-  if ((D.bugs & MR_F_BUG_STALE_READ) && D.lin32 && (opkey & 3u) == KV_GET) {
+  if ((p_bugs(D, x) & MR_F_BUG_STALE_READ) && D.lin32 && (opkey & 3u) == KV_GET) {
     // the buggy leader answers from its own state at once: no log entry, no quorum
     const uint32_t key = (opkey >> 2) & 63u, e = elem & 0xFFFFFFu;
     const uint32_t* kr = KVP(me) + KVR_KEYS + (D.lin15 ? KV_KW15 * (key & 15u) : KV_KW * key);
@@ -480,7 +480,7 @@ DI void kv_apply_lin15(const Dev& D, X& x, uint32_t me, uint32_t* kp, uint32_t k
     out = (ws & 0xFFFu) | ((~ws >> 31) << 31);
     return;
   }
-  if (!(seq > ded || (D.bugs & MR_F_BUG_NO_DEDUP))) return;  // a duplicate
+  if (!(seq > ded || (p_bugs(D, x) & MR_F_BUG_NO_DEDUP))) return;  // a duplicate
   if (cli >= LIN_CLI) { fail(D, x, MR_FAIL_SIM_CAPACITY); return; }
   const uint32_t len = 5u + ndig(cli) + ndig(j);
   if (op == KV_PUT) {  // the value is this one token
@@ -535,7 +535,7 @@ DI void kv_apply(const Dev& D, X& x, uint32_t me, uint32_t i, uint64_t v, uint32
       if (op == KV_GET) {
         outh = ((uint64_t)k[1] << 32) | k[0];
         out = kv_get_value(k, elem);
-      } else if (seq > pded || (D.bugs & MR_F_BUG_NO_DEDUP)) {
+      } else if (seq > pded || (p_bugs(D, x) & MR_F_BUG_NO_DEDUP)) {
         if (op == KV_PUT) {  // elem = the value's token (0 = "")
           const uint64_t h = elem ? (elem + 1ull) * 0x9E3779B97F4A7C15ull : 0ull;
           reinterpret_cast<uint4*>(kr)[0] = make_uint4((uint32_t)h, (uint32_t)(h >> 32), put_len(elem), 0u);

@@ -43,7 +43,7 @@ DI uint64_t t_entry(const Dev& D, X& x) {  // tests.rs:943-951 gen_entry
 // other server the draw only advances the tester's counter (draw k is keyed by k alone,
 // SEMANTICS §2; MR_TAPE builds record every draw and take it)
 DI uint64_t t_entry_for_start(const Dev& D, X& x, uint32_t i, uint32_t lm) {
-  if (!MR_TAPE && !(bit(x.alive, i) && !D.null_raft && bit(lm, i))) {
+  if (!MR_TAPE && !(bit(x.alive, i) && !p_null_raft(D, x) && bit(lm, i))) {
     x.t_ctr++;
     return 0;
   }
@@ -68,7 +68,7 @@ DI bool col_step(const Dev& D, X& x, T& t) {
     for (uint32_t i = 0; i < D.n; i++) {
       if (!t_connected(D, x, i)) continue;
       if (!t_started(D, x, i)) { fail(D, x, MR_FAIL_UNWRAP_NONE); return false; }
-      if (D.null_raft || !bit(t_leaders(D, x), i)) continue;
+      if (p_null_raft(D, x) || !bit(t_leaders(D, x), i)) continue;
       uint32_t ti = sel_nb(tm, i);
       for (uint32_t j = 0; j < i; j++) {  // >1 leaders in one term?
         if (t_connected(D, x, j) && bit(t_leaders(D, x), j) &&
@@ -108,7 +108,7 @@ DI bool one_step(const Dev& D, X& x, T& t) {
         // servers before it answer Err(NotLeader) with no effect, so one start() per lane — one
         // copy of its path per wave, not one per server index (t_start_round)
         const uint32_t all = (1u << D.n) - 1u, cand = lm & x.conn & x.alive & all;
-        if (cand && !D.null_raft) {
+        if (cand && !p_null_raft(D, x)) {
           const uint32_t r = (starts + 1u) % D.n;  // rotate so that server r is bit 0
           const uint32_t rot = ((cand >> r) | (cand << (D.n - r))) & all;
           starts = (r + (uint32_t)__builtin_ctz(rot)) % D.n;
@@ -232,7 +232,7 @@ DI void scn_many_election(const Dev& D, X& x, T& t) {  // tests.rs:80-112
     case 0: t_new(D, x, false); COL_TO(1)
     case 1: it = 0; GO(2)
     case 2:
-      if (it >= D.iters) COL_TO(4)
+      if (it >= p_iters(D, x)) COL_TO(4)
       i1 = t_range(D, x, 0, n); i2 = t_range(D, x, 0, n); i3 = t_range(D, x, 0, n);
       t_conn(D, x, i1, 0); t_conn(D, x, i2, 0); t_conn(D, x, i3, 0);
       COL_TO(3)
@@ -618,7 +618,7 @@ DI uint32_t fig8_delay(const Dev& D, X& x) {  // tests.rs:631-635 / 711-715
 DI uint32_t t_start_round(const Dev& D, X& x, uint32_t iter, bool need_conn) {
   const uint32_t lm = t_leaders(D, x), ctr0 = x.t_ctr;
   uint32_t res = NONE;
-  if (MR_TAPE || D.null_raft || (iter & ~x.alive)) {  // server by server
+  if (MR_TAPE || p_null_raft(D, x) || (iter & ~x.alive)) {  // server by server
     for (uint32_t i = 0; i < D.n; i++) {
       if (!bit(iter, i)) continue;
       const uint64_t e = t_entry_for_start(D, x, i, lm);
@@ -655,7 +655,7 @@ DI void scn_figure_8(const Dev& D, X& x, T& t, bool unreliable) {
       ONE_TO(t_entry(D, x), 1, true, 1)
     case 1: nup = n; it = 0; GO(2)
     case 2:
-      if (it >= D.iters) {
+      if (it >= p_iters(D, x)) {
         for (uint32_t i = 0; i < n; i++)
           if (!t_started(D, x, i)) t_start1(D, x, i);
         ONE_TO(t_entry(D, x), n, true, 4)
@@ -688,7 +688,7 @@ DI void scn_figure_8_unreliable(const Dev& D, X& x, T& t) {  // tests.rs:688-741
       ONE_TO(t_entry(D, x), 1, true, 1)
     case 1: nup = n; it = 0; GO(2)
     case 2:
-      if (it >= D.iters) {
+      if (it >= p_iters(D, x)) {
         for (uint32_t i = 0; i < n; i++) t_conn(D, x, i, 1);
         ONE_TO(t_entry(D, x), n, true, 4)
       }
@@ -725,7 +725,7 @@ DI void scn_snap_common(const Dev& D, X& x, T& t, bool disconnect, bool reliable
     case 1: COL_TO(2)
     case 2: leader1 = t.res; i = 0; GO(3)
     case 3:
-      if (i >= D.iters) END()
+      if (i >= p_iters(D, x)) END()
       victim = (i % 3 == 1) ? leader1 : (leader1 + 1) % n;
       if (disconnect) { t_conn(D, x, victim, 0); ONE_TO(t_entry(D, x), n - 1, true, 4) }
       GO(4)

@@ -64,6 +64,8 @@ def lib():
                                               C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                               C.c_void_p]
     L.mr_batch_set_seeds.argtypes = [C.c_void_p, C.c_void_p]
+    L.mr_batch_set_param_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.mr_batch_group_counters.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MrCounters)]
     L.mr_batch_get_decisions_packed.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_size_t]
     L.mr_decision_word.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
@@ -163,6 +165,18 @@ def seed_offsets(seeds, seed_base, cluster_base=0):
     return np.array(off, np.uint32)
 
 
+def param_group_records(groups):
+    """PARAM_GROUP_DTYPE records of a list of dicts with mr_param_group's field names (None: none)."""
+    names = set(_abi.PARAM_GROUP_DTYPE.names) - {"reserved"}
+    g = np.zeros(len(groups or []), _abi.PARAM_GROUP_DTYPE)
+    for i, d in enumerate(groups or []):
+        if set(d) - names:
+            raise SimError(f"parameter group {i}: unknown field(s) {sorted(set(d) - names)}")
+        for k, v in d.items():
+            g[i][k] = int(v)
+    return g
+
+
 class Batch:
     """`clusters` seeds of one reference test, resident on one GPU."""
 
@@ -234,6 +248,27 @@ class Batch:
             if off.shape != (self.clusters,):
                 raise SimError(f"seeds: shape {off.shape}, not ({self.clusters},)")
         _check(lib().mr_batch_set_seeds(self._b, off.ctypes.data if off is not None else None))
+
+    def set_param_groups(self, groups, group_of=None):
+        """Position c runs under the settings of groups[group_of[c]] (mr_batch_set_param_groups;
+        docs/SEMANTICS.md §12.4): `groups` is a list of dicts with mr_param_group's field names
+        (flags, hb_us, elect_lo_us, elect_hi_us, ae_max, iters; a missing or zero number = the
+        batch's, `flags` = the group's SWEEPABLE_FLAGS bits, which replace the batch's). None or
+        empty = the batch's cfg everywhere again. The groups stay through reset(), set_seeds() and
+        every set_decisions() / set_variants*()."""
+        g = param_group_records(groups)
+        of = None
+        if g.size:
+            of = np.ascontiguousarray(group_of, dtype=np.uint32)
+            if of.shape != (self.clusters,):
+                raise SimError(f"group_of: shape {of.shape}, not ({self.clusters},)")
+        _check(lib().mr_batch_set_param_groups(self._b, _ptr(g), g.size, _ptr(of)))
+
+    def group_counters(self, g):
+        """counters() restricted to the positions of parameter group g (mr_batch_group_counters)."""
+        c = MrCounters()
+        _check(lib().mr_batch_group_counters(self._b, int(g), C.byref(c)))
+        return c.to_dict()
 
     def _set_tables(self, rc, n_edits=0):
         """After a call that replaces or drops the decision tables: `n_edits` = the mask columns
@@ -437,6 +472,83 @@ def run_seeds(test, seeds, **kw):
         cnt = b.counters()
     _print_failures(test, code, t, lambda k: seeds[k])
     return code, t, dig, cnt
+
+
+def sweep_groups(grid):
+    """The parameter groups of a sweep: the cartesian product of `grid`'s value lists, in the order
+    given (the last field varies fastest). `grid` maps hb_us, ae_max or iters to numbers, elect_us
+    to (lo, hi) pairs, bug to the names in _abi.BUG_FLAGS, unreliable / null_raft to booleans.
+    Returns (params, groups): per setting the dict of what the grid set, and its mr_param_group
+    fields for Batch.set_param_groups."""
+    params, groups = [{}], [{"flags": 0}]
+    for field, values in grid.items():
+        values = list(values)
+        if not values:
+            raise SimError(f"sweep: no values for {field!r}")
+        np_, ng = [], []
+        for p, g in zip(params, groups):
+            for v in values:
+                g2 = dict(g)
+                if field in ("hb_us", "ae_max", "iters"):
+                    v = int(v)
+                    g2[field] = v
+                elif field == "elect_us":
+                    v = (int(v[0]), int(v[1]))
+                    g2["elect_lo_us"], g2["elect_hi_us"] = v
+                elif field == "bug":
+                    if v not in _abi.BUG_FLAGS:
+                        raise SimError(f"sweep: unknown bug {v!r}")
+                    g2["flags"] |= _abi.BUG_FLAGS[v]
+                elif field in ("unreliable", "null_raft"):
+                    v = bool(v)
+                    bit = _abi.MR_F_UNRELIABLE if field == "unreliable" else _abi.MR_F_NULL_RAFT
+                    g2["flags"] |= bit if v else 0
+                else:
+                    raise SimError(f"sweep: unknown field {field!r}")
+                np_.append({**p, field: v})
+                ng.append(g2)
+        params, groups = np_, ng
+    return params, groups
+
+
+def sweep_positions(n_groups, seeds):
+    """(group_of, seed_of) of a sweep batch in group-minor order: position p is group p % G at seed
+    seeds[p // G], so every wave mixes the groups and every group runs the same seeds."""
+    p = np.arange(n_groups * len(seeds))
+    return (p % n_groups).astype(np.uint32), [int(seeds[i]) for i in p // n_groups]
+
+
+def run_sweep(test, grid, seeds=None, num=None, **kw):
+    """Every setting of `grid` (sweep_groups) over the same seeds in one batch of parameter groups
+    (docs/SEMANTICS.md §12.4). Seeds: the list `seeds`, else `num` seeds from kw's `seed` (default:
+    the README's). The batch-wide sweepable flags in kw (unreliable, null_raft, bug bits in flags) are
+    the default of every group that does not set them. Returns one dict per setting: params, group
+    (the mr_param_group fields), seeds, codes, times_us, digests, counters (group_counters)."""
+    kw = dict(kw)
+    first = int(kw.pop("seed", _abi.README_SEED))
+    seeds = [int(s) for s in seeds] if seeds is not None else [first + k for k in range(int(num or 1))]
+    if not seeds:
+        raise SimError("run_sweep: no seeds")
+    params, groups = sweep_groups(grid)
+    base_c = int(kw.pop("cluster_base", 0))
+    with Batch(test, len(groups) * len(seeds), min(seeds) - base_c, cluster_base=base_c, **kw) as b:
+        inherit = int(b.cfg.flags) & _abi.SWEEPABLE_FLAGS
+        for g in groups:  # a group's flags replace the batch's: what the grid left alone stays
+            if "bug" not in grid:
+                g["flags"] |= inherit & ~(_abi.MR_F_UNRELIABLE | _abi.MR_F_NULL_RAFT)
+            if "unreliable" not in grid:
+                g["flags"] |= inherit & _abi.MR_F_UNRELIABLE
+            if "null_raft" not in grid:
+                g["flags"] |= inherit & _abi.MR_F_NULL_RAFT
+        G = len(groups)
+        group_of, seed_of = sweep_positions(G, seeds)
+        b.set_seeds(seed_of)
+        b.set_param_groups(groups, group_of)
+        b.run()
+        code, t, dig = b.verdicts()
+        return [{"params": params[g], "group": groups[g], "seeds": seeds, "codes": code[g::G],
+                 "times_us": t[g::G], "digests": dig[g::G], "counters": b.group_counters(g)}
+                for g in range(G)]
 
 
 def run_test(test, seed=None, num=None, **kw):
