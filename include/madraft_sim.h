@@ -607,6 +607,40 @@ int mr_batch_set_param_groups(mr_batch* b, const mr_param_group* g, size_t n_gro
  * first_fail_cluster = its first failing position + cluster_base (UINT64_MAX: none). An error if
  * `group` is out of range or no groups are set. */
 int mr_batch_group_counters(mr_batch* b, uint32_t group, mr_counters* out);
+/* ---- fork (an addition within ABI 7, docs/SEMANTICS.md §12.5) ----
+ * Position c of dst becomes a copy of position src_of[c] of src as that cluster stands now; src may
+ * be dst. src_of[c] == UINT32_MAX leaves c as it is (and so does src_of[c] == c when src == dst).
+ * Every later draw of c follows c's own rule in dst: its seed seed_base + cluster_base + c, or its
+ * seed-list entry, its lookup slice or its parameter group. The whole run of c then equals the run
+ * of c's seed with the decisions the source had drawn (what MR_F_RECORD records of it) set as keyed
+ * decisions: verdict, time, digest, trace and per-cluster counters. The batches may differ in
+ * n_clusters, trace_clusters, trace_cap, tape_cap, seeds, timers, iters and lanes. The call blocks;
+ * afterwards dst's launch loop starts over (positions with a verdict are skipped at one load each).
+ * When both batches record, the source's tape comes along, so a forked position's tape is its whole
+ * history; otherwise the position's count of draws (mr_batch_get_decisions' n) restarts at 0.
+ * Counters: events, msgs_sent, virt_time_us, done / passed / failed, fail_hist, first_fail_*, both
+ * coverage histograms and the kv_* counters are kept per cluster, are copied, and speak of each
+ * position's whole history. So do the rows of MR_COUNTER_TABLE when the prefix ran on "step_kernel"
+ * or "step_kernel_tape". "pool_kernel" sums those rows per workgroup into the batch that ran them:
+ * a prefix run there stays counted once, in the source's batch, and the destination adds the
+ * futures to whatever its own earlier launches since its reset summed (nothing, for a destination
+ * not launched before the fork); leaders_elected and max_index travel with the cluster there too.
+ * Errors, all found before anything is written, so both batches stay as they were: a null
+ * argument; a submitted step not yet finished on either batch; different device, scenario, n_nodes,
+ * log_cap, apply_cap, msg_slots, ae_max, MR_F_SAFETY or the MR_KEY_ROWS they were created under;
+ * src_of[c] >= src's n_clusters; src == dst
+ * and a source that is itself overwritten; src's launches since its reset wrote the message keys
+ * in one format ("pool_kernel"'s, or the one "step_kernel" and "step_kernel_tape" share) and dst's
+ * kernel reads the other ("source ran on ..., destination continues on ..."; a source not launched
+ * since its reset is always accepted); a traced position of dst (c < trace_clusters) whose source is
+ * not traced, holds more records than dst's trace_cap, or has drawn more than its own trace_cap
+ * when the two caps differ (it dropped records dst would hold); a recording dst with a src that does not
+ * record. */
+int mr_batch_fork(mr_batch* dst, mr_batch* src, const uint32_t* src_of /* [dst n_clusters] */);
+/* A measurement aid: the device time of fork_kernel in b's last mr_batch_fork as destination.
+ * Meaningful only directly after that fork: an error once b has been reset or launched since, or if
+ * it was never forked into (or the fork copied nothing). */
+int mr_batch_fork_ms(mr_batch* b, float* ms);
 /* One cluster of cfg (cluster_base selects the seed for misses) driven by the n decisions:
  * its per-event trace (per-node term / role / commit / applied / last / snapshot after every
  * event), its verdict and verdict time, and (misses != NULL) its draws not in `d`. */

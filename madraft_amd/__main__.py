@@ -7,7 +7,10 @@ analogue of `MADSIM_TEST_SEED=S MADSIM_TEST_NUM=N cargo test <test>`;
 variant batch of groups, one launch per ddmin round for all of them; `--seeds LIST` (or `@file`)
 runs exactly those seeds in one batch (docs/SEMANTICS.md §12.3), and with `--shrink` shrinks them;
 `--sweep FIELD=V1,V2,...` (repeatable) runs every combination of the settings over the same seeds
-in one batch of parameter groups (§12.4) and prints one JSON line per setting."""
+in one batch of parameter groups (§12.4) and prints one JSON line per setting;
+`--seed S --fork-at EVENTS --futures N` runs seed S for EVENTS events, forks that state into N
+positions (§12.5) and prints the futures' verdict histogram and, per failing future, the
+`sim.replay` call that reproduces it."""
 import argparse
 import json
 import time
@@ -119,7 +122,19 @@ def main(argv=None):
     ap.add_argument("--sweep", action="append", default=[], metavar="FIELD=V1,V2,...",
                     help="sweep a setting over the same seeds in one batch (repeatable: every "
                          "combination): hb_us, ae_max, iters, elect_us=lo:hi,..., bug=none,NAME,...")
+    ap.add_argument("--fork-at", type=int, default=None, metavar="EVENTS",
+                    help="with --futures: run --seed for EVENTS events, then fork that state")
+    ap.add_argument("--futures", type=int, default=None, metavar="N",
+                    help="with --fork-at: the positions the state is forked into, each continuing "
+                         "from its own seed (--seed + position)")
+    ap.add_argument("--fork-tape", metavar="LOG",
+                    help="with --fork-at: write the prefix's tape as a raw --replay log")
     a = ap.parse_args(argv)
+    if (a.fork_at is None) != (a.futures is None):
+        ap.error("--fork-at and --futures go together")
+    if a.fork_at is not None and (a.replay or a.shrink or a.shrink_failures is not None or a.sweep
+                                  or a.seeds):
+        ap.error("--fork-at does not go with --replay, --shrink, --shrink-failures, --sweep or --seeds")
     grid = None
     if a.sweep:
         if a.replay or a.shrink or a.shrink_failures is not None:
@@ -186,6 +201,24 @@ def main(argv=None):
                               "launches": res.launches,
                               "kept_sizes": sorted({int(r.kept.size) for r in done})}))
         raise SystemExit(0)
+    if a.fork_at is not None:
+        seed = _abi.README_SEED if a.seed is None else a.seed
+        r = sim.run_futures(a.test, seed, a.fork_at, a.futures, **cfg_kw)
+        if a.fork_tape:
+            trace.dump_jsonl(a.fork_tape, r["prefix"], raw=True)
+        cnt = r["counters"]
+        print(json.dumps({"seed": seed, "fork_at": a.fork_at, "futures": a.futures,
+                          "prefix_decisions": int(r["prefix"].size), "kernel": r["kernel"],
+                          "passed": cnt["passed"], "failed": cnt["failed"],
+                          "fail_hist": cnt["fail_hist"]}))
+        extra = "".join(f", {k}={v!r}" for k, v in cfg_kw.items() if v)
+        for c in (r["codes"] != _abi.MR_PASS).nonzero()[0]:
+            print(json.dumps({"position": int(c), "code": int(r["codes"][c]),
+                              "verdict": _abi.FAIL_NAMES.get(int(r["codes"][c]), str(r["codes"][c])),
+                              "time_us": int(r["times_us"][c]),
+                              "replay": f"sim.replay({a.test!r}, prefix, seed={seed}, "
+                                        f"cluster_base={int(c)}{extra})"}))
+        raise SystemExit(1 if cnt["failed"] else 0)
     if grid:
         seeds = a.seeds or [(_abi.README_SEED if a.seed is None else a.seed) + k
                             for k in range(a.clusters or 1)]

@@ -198,4 +198,6 @@ EXPORTS = [
     "mr_batch_set_variant_groups",  # ABI 6
     "mr_batch_set_seeds", "mr_batch_get_decisions_packed",  # ABI 7
     "mr_batch_set_param_groups", "mr_batch_group_counters",  # parameter groups (within ABI 7)
+    "mr_batch_fork", "mr_batch_fork_ms",  # fork (within ABI 7)
 ]
+FORK_SKIP = 0xFFFFFFFF  # mr_batch_fork's src_of[c]: position c stays as it is

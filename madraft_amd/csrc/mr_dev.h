@@ -402,43 +402,51 @@ constexpr bool restarts_servers(uint32_t s) {
          s == MR_SCN_SNAPSHOT_INSTALL_UNRELIABLE_CRASH_2D || s == MR_SCN_FIGURE_8_UNRELIABLE_CRASH;
 }
 // ---- the batch's device arrays, one row each, in the order they are carved from the batch's one
-// allocation (every array 256-B aligned): X(Dev member, elements, present, reset)
-//   elements  over the config: C clusters, n servers, M message slots, K = ae_max, log_cap, apply_cap,
-//             trace_clusters (0 unless MR_F_TRACE), trace_cap, safety (1 with MR_F_SAFETY, else 0), and
-//             the scenario s (nthr(s) thread slots, kws() of them for the scheduler keys)
+// allocation (every array 256-B aligned): X(Dev member, owner(elements per owner), present, reset)
+//   owner     whose state the row is, and with it how many times its elements repeat:
+//             MR_MINOR(w): a cluster-minor matrix [w][C], field f of cluster c at f * C + c;
+//             MR_MAJOR(w): cluster-major records [C][w], cluster c's slab at c * w;
+//             MR_TRACED(w): as MR_MAJOR for the traced clusters only, [trace_clusters][w];
+//             MR_SHARED(w): w elements of the batch, no cluster's state
+//             (the first three are what mr_batch_fork copies; a row without an owner does not compile:
+//             its element count names no C, and is no OwnKind for k_dev_own)
+//   elements  per owner, over the config: n servers, M message slots, K = ae_max, log_cap, apply_cap,
+//             trace_cap, safety (1 with MR_F_SAFETY, else 0), and the scenario s (nthr(s) thread slots,
+//             kws() of them for the scheduler keys). The array holds them x C clusters, or x
+//             trace_clusters (0 unless MR_F_TRACE), or once (dev_layout)
 //   present   over s; an absent or empty array is a null pointer
 //   reset     ZERO(k): the k-th memset of mr_batch_reset; KERNEL: reset_kernel initialises it; NONE: a
 //             run writes it before it reads it (the row says why); GUARD: ZERO in MR_GUARD builds
 #define MR_DEV_ARRAYS(X)                                                                          \
-  X(cs32, CS_STRIDE * C, true, KERNEL)                                                            \
-  X(cs64, C64_STRIDE * C, true, KERNEL)                                                           \
-  X(nd32, NREC * n * C, true, KERNEL)                                                             \
-  X(tmr, n * C, true, KERNEL)                                                                     \
-  X(ms32, MREC * M * C, true, NONE) /* a slot's record is written when its key is: at the send */ \
-  X(mkey, M * C, true, KERNEL)                                                                    \
-  X(log, C * n * log_cap, true, NONE) /* entries up to NF_LAST, each written by its append */     \
-  X(pay, C * M * K, true, NONE)       /* written when the slot's message takes a payload */       \
-  X(stor, C * apply_cap, true, ZERO(2))                                                           \
-  X(kt32, KT_STRIDE * nthr(s) * C, nthr(s) > 0, KERNEL)                                           \
-  X(kwk, 2 * kws(nthr(s)) * C, nthr(s) > 0, KERNEL)                                               \
-  X(kv32, KVREC * n * C, is_svc(s), ZERO(7))                                                      \
-  X(lin32, KV_KEYS * KV_APP * LINW * C, is_kv(s), ZERO(8))                                        \
-  X(kvs32, KVS_W * n * C, kv_gen(s).maxraft > 0, ZERO(9))                                         \
-  X(kring, KRW * KV_RING * C, kv_gen(s).maxraft > 0, ZERO(10))                                    \
-  X(cfg32, CFG_CAP * CFGW * n * C, is_ctrl(s), KERNEL)                                            \
-  X(op32, OP_CAP * OPW * C, is_ctrl(s), NONE) /* rows below CS_NOPS, each written by its clerk */ \
-  X(cval, 3 * CHURN_VCAP * C, mr_scn_is_churn(s), NONE) /* up to the client's own count */        \
-  X(cidx, 3 * CHURN_VCAP * C, mr_scn_is_churn(s), NONE) /* as cval */                             \
-  X(led, safety * LED_W * C, true, ZERO(3))                                                            \
-  X(trace, trace_clusters * trace_cap, true, NONE) /* records below CS_TRACEN */                  \
-  X(tdig, trace_clusters * trace_cap, true, ZERO(4))                                              \
-  X(tapp, trace_clusters * trace_cap * 2, true, ZERO(5))                                          \
-  X(adig, trace_clusters * MR_MAX_NODES * 2, true, ZERO(6))                                       \
-  X(remaining, 2, true, NONE)  /* copied from the host before every launch */                     \
-  X(prof, PROF_SLOTS, true, NONE) /* zeroed at create: a profile sums over the batch's runs */    \
-  X(guard, 4, true, GUARD)        /* zeroed at create */                                          \
-  X(pcnt, CNT__N, true, ZERO(0))                                                                  \
-  X(tfr, TF_Q * C, true, KERNEL)
+  X(cs32, MR_MINOR(CS_STRIDE), true, KERNEL)                                                      \
+  X(cs64, MR_MINOR(C64_STRIDE), true, KERNEL)                                                     \
+  X(nd32, MR_MAJOR(NREC * n), true, KERNEL)                                                       \
+  X(tmr, MR_MINOR(n), true, KERNEL)                                                               \
+  X(ms32, MR_MAJOR(MREC * M), true, NONE) /* a slot's record is written when its key is: at the send */ \
+  X(mkey, MR_MINOR(M), true, KERNEL)                                                              \
+  X(log, MR_MAJOR(n * log_cap), true, NONE) /* entries up to NF_LAST, each written by its append */ \
+  X(pay, MR_MAJOR(M * K), true, NONE)       /* written when the slot's message takes a payload */  \
+  X(stor, MR_MAJOR(apply_cap), true, ZERO(2))                                                     \
+  X(kt32, MR_MAJOR(KT_STRIDE * nthr(s)), nthr(s) > 0, KERNEL)                                     \
+  X(kwk, MR_MAJOR(2 * kws(nthr(s))), nthr(s) > 0, KERNEL)                                         \
+  X(kv32, MR_MAJOR(KVREC * n), is_svc(s), ZERO(7))                                                \
+  X(lin32, MR_MAJOR(KV_KEYS * KV_APP * LINW), is_kv(s), ZERO(8))                                  \
+  X(kvs32, MR_MAJOR(KVS_W * n), kv_gen(s).maxraft > 0, ZERO(9))                                   \
+  X(kring, MR_MAJOR(KRW * KV_RING), kv_gen(s).maxraft > 0, ZERO(10))                              \
+  X(cfg32, MR_MAJOR(CFG_CAP * CFGW * n), is_ctrl(s), KERNEL)                                      \
+  X(op32, MR_MAJOR(OP_CAP * OPW), is_ctrl(s), NONE) /* rows below CS_NOPS, each written by its clerk */ \
+  X(cval, MR_MAJOR(3 * CHURN_VCAP), mr_scn_is_churn(s), NONE) /* up to the client's own count */  \
+  X(cidx, MR_MAJOR(3 * CHURN_VCAP), mr_scn_is_churn(s), NONE) /* as cval */                       \
+  X(led, MR_MAJOR(safety * LED_W), true, ZERO(3))                                                 \
+  X(trace, MR_TRACED(trace_cap), true, NONE) /* records below CS_TRACEN */                        \
+  X(tdig, MR_TRACED(trace_cap), true, ZERO(4))                                                    \
+  X(tapp, MR_TRACED(trace_cap * 2), true, ZERO(5))                                                \
+  X(adig, MR_TRACED(MR_MAX_NODES * 2), true, ZERO(6))                                             \
+  X(remaining, MR_SHARED(2), true, NONE)  /* copied from the host before every launch */          \
+  X(prof, MR_SHARED(PROF_SLOTS), true, NONE) /* zeroed at create: a profile sums over the batch's runs */ \
+  X(guard, MR_SHARED(4), true, GUARD)        /* zeroed at create */                               \
+  X(pcnt, MR_SHARED(CNT__N), true, ZERO(0))                                                       \
+  X(tfr, MR_MAJOR(TF_Q), true, KERNEL)
 #define MR_ROW_(m, elements, present, reset) A_##m,
 enum DevArray : uint32_t { MR_DEV_ARRAYS(MR_ROW_) A__N };
 #undef MR_ROW_
@@ -452,6 +460,22 @@ constexpr int RST_NONE = -2, RST_KERNEL = -1;  // (a ZERO row: its place k)
 #define MR_ROW_(m, elements, present, reset) RST_##reset,
 constexpr int k_dev_reset[A__N] = {MR_DEV_ARRAYS(MR_ROW_)};  // by DevArray
 #undef MR_ROW_
+// whose state a row is (its owner column), by DevArray: the one place the fork, the layout and the
+// checks read it from
+enum OwnKind : uint32_t { OWN_MINOR, OWN_MAJOR, OWN_TRACED, OWN_SHARED };
+#define MR_MINOR(w) OWN_MINOR
+#define MR_MAJOR(w) OWN_MAJOR
+#define MR_TRACED(w) OWN_TRACED
+#define MR_SHARED(w) OWN_SHARED
+#define MR_ROW_(m, elements, present, reset) elements,
+constexpr OwnKind k_dev_own[A__N] = {MR_DEV_ARRAYS(MR_ROW_)};  // by DevArray
+#undef MR_ROW_
+#undef MR_MINOR
+#undef MR_MAJOR
+#undef MR_TRACED
+#undef MR_SHARED
+// a cluster's state between launches is the rows owned per cluster or per traced cluster
+constexpr bool own_is_cluster(OwnKind k) { return k != OWN_SHARED; }
 // a batch of scenario s has array a: the kernels' template constant S folds it, so an array's
 // presence is typed out in its row only
 constexpr bool dev_has(uint32_t s, DevArray a) {
@@ -467,18 +491,36 @@ constexpr void scenario_fixed(Dev& D, uint32_t s) {
   D.lin15 = mr_scn_is_lin15(s) ? 1u : 0u;  // generic_test_linearizability layout (SEMANTICS §9b)
 }
 // Where a batch of config c keeps its arrays: a function of the config alone, so it is checked
-// without a device (tests/test_abi.py). bytes 0: absent or empty; off[A__N]: the allocation's size
-struct DevLayout { size_t bytes[A__N], off[A__N + 1]; };
+// without a device (tests/test_abi.py, tests/test_fork_host.py). per: the bytes one owner has of the
+// array (a cluster, a traced cluster, or the batch for an OWN_SHARED row); bytes = per x the row's
+// owners, 0: absent or empty; off[A__N]: the allocation's size
+struct DevLayout { size_t per[A__N], bytes[A__N], off[A__N + 1]; };
+// owners of a row of kind k in a batch of C clusters of which trace_clusters are traced
+constexpr uint64_t dev_owners(OwnKind k, uint64_t C, uint64_t trace_clusters) {
+  return k == OWN_SHARED ? 1u : k == OWN_TRACED ? trace_clusters : C;
+}
 inline DevLayout dev_layout(const mr_cfg& c) {
   const uint64_t C = c.n_clusters, n = c.n_nodes, M = c.msg_slots, K = c.ae_max, log_cap = c.log_cap,
                  apply_cap = c.apply_cap, trace_cap = c.trace_cap, trace_clusters = (c.flags & MR_F_TRACE) ? c.trace_clusters : 0u;
   const uint32_t s = c.scenario, safety = (c.flags & MR_F_SAFETY) ? 1u : 0u;
   DevLayout L{};
+#define MR_MINOR(w) (w)
+#define MR_MAJOR(w) (w)
+#define MR_TRACED(w) (w)
+#define MR_SHARED(w) (w)
 #define MR_ROW_(m, elements, present, reset) \
-  L.bytes[A_##m] = dev_has(s, A_##m) ? (elements) * sizeof(*Dev().m) : 0u;
+  L.per[A_##m] = dev_has(s, A_##m) ? (uint64_t)(elements) * sizeof(*Dev().m) : 0u;
   MR_DEV_ARRAYS(MR_ROW_)
 #undef MR_ROW_
-  for (uint32_t a = 0; a < A__N; a++) L.off[a + 1] = L.off[a] + ((L.bytes[a] + 255) & ~size_t(255));
+#undef MR_MINOR
+#undef MR_MAJOR
+#undef MR_TRACED
+#undef MR_SHARED
+  for (uint32_t a = 0; a < A__N; a++) {
+    L.bytes[a] = L.per[a] * dev_owners(k_dev_own[a], C, trace_clusters);
+    if (!L.bytes[a]) L.per[a] = 0;  // (no owner: absent)
+    L.off[a + 1] = L.off[a] + ((L.bytes[a] + 255) & ~size_t(255));
+  }
   return L;
 }
 // D's array members point into the allocation at `base` as L lays it out
@@ -488,6 +530,43 @@ inline void dev_carve(Dev& D, const DevLayout& L, char* base) {
   MR_DEV_ARRAYS(MR_ROW_)
 #undef MR_ROW_
 }
+
+// ---- mr_batch_fork (SEMANTICS §12.5): what fork_kernel (mr_fork.inc) is told, its own argument —
+// Dev does not change for it. One ForkRow per array of the table that both batches have and that
+// is some cluster's state, as the host walks the table, and one for the record tape.
+enum ForkKind : uint32_t { FK_MINOR, FK_MAJOR, FK_TAPE };  // (OWN_TRACED rows are FK_MAJOR over the traced)
+constexpr uint32_t FORK_SKIP = ~0u;  // src_of[c]: position c stays as it is
+constexpr uint32_t FORK_BLOCK = 256, FORK_QUADS = 4 * FORK_BLOCK, FORK_FIELDS = 8;
+struct ForkRow {
+  char* dst;
+  const char* src;
+  uint32_t kind;    // a ForkKind
+  uint32_t owners;  // destination owners: its clusters, or its traced clusters
+  uint32_t dper;    // FK_MINOR: fields; else the bytes one owner has in the destination (16-B quads)
+  uint32_t sper;    // ... in the source
+  uint32_t esz;     // FK_MINOR: bytes of an element, 4 or 8
+  uint32_t zfield;  // FK_MINOR: the field that becomes 0 in every forked position, ~0u: none
+  uint32_t blk0;    // the row's first block of the launch
+  uint32_t pad;
+};
+constexpr uint32_t FORK_ROWS = A__N + 1;
+struct ForkPlan {
+  const uint32_t* src_of;     // [Cd] the destination positions' sources, FORK_SKIP: none
+  const uint32_t* tape_used;  // FK_TAPE: the source's CS_TAPE row, [Cs]
+  uint32_t Cd, Cs;            // clusters of the destination and of the source: the FK_MINOR strides
+  uint32_t n_rows, blocks;    // rows in use; the launch's blocks = the last row's end
+  ForkRow row[FORK_ROWS];
+};
+// blocks of FORK_BLOCK threads a row takes (mr_fork.inc says how they divide it)
+constexpr uint64_t fork_blocks(const ForkRow& r) {
+  if (r.kind == FK_MINOR)
+    return (uint64_t)((r.dper + FORK_FIELDS - 1) / FORK_FIELDS) * ((r.owners + FORK_BLOCK - 1) / FORK_BLOCK);
+  const uint32_t q = r.dper / 16u;
+  if (q >= FORK_QUADS || r.kind == FK_TAPE) return (uint64_t)r.owners * ((q + FORK_QUADS - 1) / FORK_QUADS);
+  const uint32_t opb = FORK_QUADS / q;  // owners per block
+  return ((uint64_t)r.owners + opb - 1) / opb;
+}
+hipError_t launch_fork(const ForkPlan& P, hipStream_t s);
 
 #define MR_INST_ROW_(id, sym, name, n, kind, slots, exact, pool) MR_INST(id)
 #define MR_ALL_SCNS MR_SCENARIO_TABLE(MR_INST_ROW_)  // MR_INST(id) for every row of the table

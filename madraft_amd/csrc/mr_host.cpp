@@ -209,6 +209,7 @@ struct mr_batch {
   DevMem<uint32_t> sof;          // the seed list (mr_batch_set_seeds): the batch's, not its tables'
   ParamGroups pg;                // the parameter groups (mr_batch_set_param_groups): the batch's too
   RunState run;
+  bool fork_timed = false;  // ev0 / ev1 bracket a fork_kernel: no reset or step since (mr_batch_fork_ms)
 };
 struct BatchDestroy {
   void operator()(mr_batch* b) const { mr_batch_destroy(b); }
@@ -408,7 +409,14 @@ static int mr_batch_create_impl(const mr_cfg* cfg, mr_batch** out) {
   return 0;
 }
 
+// the key format the batch's next launch reads and writes: its kernel family's
+static KeyFormat key_format_of(const Dev& D) { return family_of(D) == F_POOL ? KEYS_POOL : KEYS_STEP; }
+static const char* key_format_name(KeyFormat k) {
+  return k == KEYS_POOL ? "pool_kernel" : "step_kernel / step_kernel_tape";
+}
+
 static int enqueue_reset(mr_batch* b, uint64_t seed_base) {
+  b->fork_timed = false;
   b->cfg.seed_base = seed_base;
   b->run = RunState{};
   b->pg.fresh = false;
@@ -430,8 +438,9 @@ static int enqueue_reset(mr_batch* b, uint64_t seed_base) {
 static int enqueue_step(mr_batch* b, uint32_t c0, uint32_t budget) {
   RunState& r = b->run;
   Dev& D = b->D;
+  b->fork_timed = false;
   // a run does not switch key format between its launches
-  const KeyFormat keys = family_of(D) == F_POOL ? KEYS_POOL : KEYS_STEP;
+  const KeyFormat keys = key_format_of(D);
   if (r.keys != KEYS_UNSET && r.keys != keys)
     return set_err("decisions set or dropped in the middle of a pool-kernel run: mr_batch_reset first");
   r.keys = keys;
@@ -1101,6 +1110,150 @@ int mr_batch_group_counters(mr_batch* b, uint32_t group, mr_counters* out) {
   unsigned long long h[RED_N];
   HIPCHK(hipMemcpy(h, b->pg.red.get() + (size_t)group * RED_N, sizeof h, hipMemcpyDeviceToHost));
   return fill_counters(b, h, b->pg.positions[group], out);
+}
+
+// bytes of one element of each array, by DevArray
+#define MR_ROW_(m, elements, present, reset) (uint32_t)sizeof(*Dev().m),
+static constexpr uint32_t k_dev_esz[A__N] = {MR_DEV_ARRAYS(MR_ROW_)};
+#undef MR_ROW_
+
+// mr_batch_fork (madraft_sim.h): everything is checked, the plan laid out and the sources uploaded
+// before fork_kernel writes, so every error leaves both batches as they were. The plan is the walk
+// of MR_DEV_ARRAYS that the reset and dev_layout make: every row that is a cluster's state
+// (k_dev_own) and that both batches hold, by its per-owner size in each (DevLayout::per).
+static int fork_impl(mr_batch* dst, mr_batch* src, const uint32_t* src_of) {
+  const mr_cfg &d = dst->cfg, &s = src->cfg;
+  const std::pair<const char*, bool> differs[] = {
+      {"device", d.device != s.device}, {"scenario", d.scenario != s.scenario},
+      {"n_nodes", d.n_nodes != s.n_nodes}, {"log_cap", d.log_cap != s.log_cap},
+      {"apply_cap", d.apply_cap != s.apply_cap}, {"msg_slots", d.msg_slots != s.msg_slots},
+      {"ae_max", d.ae_max != s.ae_max}, {"MR_F_SAFETY", ((d.flags ^ s.flags) & MR_F_SAFETY) != 0},
+      {"MR_KEY_ROWS", dst->D.krows != src->D.krows}};  // (which message keys the 7-server pool keeps in HBM)
+  for (const auto& [what, bad] : differs)
+    if (bad) return set_err(std::string("mr_batch_fork: the batches differ in ") + what);
+  const uint32_t Cd = dst->D.C, Cs = src->D.C, Td = dst->D.trace_clusters, Ts = src->D.trace_clusters;
+  const bool in_place = src == dst;
+  std::vector<uint32_t> of(src_of, src_of + Cd);  // as the kernel takes it: identity in place = skip
+  std::vector<uint32_t> tracen;                   // the source's CS_TRACEN of its traced clusters
+  bool any = false;
+  for (uint32_t c = 0; c < Cd; c++) {
+    const uint32_t from = src_of[c];
+    const std::string at = "mr_batch_fork: src_of[" + std::to_string(c) + "] = " + std::to_string(from);
+    if (from == FORK_SKIP) continue;
+    if (from >= Cs) return set_err(at + ": the source has " + std::to_string(Cs) + " clusters");
+    if (in_place && from == c) { of[c] = FORK_SKIP; continue; }
+    if (in_place && src_of[from] != FORK_SKIP && src_of[from] != from)
+      return set_err(at + ": that source is itself overwritten (src_of[" + std::to_string(from) + "] = " +
+                     std::to_string(src_of[from]) + ")");
+    if (c < Td) {
+      if (from >= Ts) return set_err(at + ": a traced position from a source that is not traced");
+      if (tracen.empty()) {
+        tracen.resize(Ts);
+        HIPCHK(hipMemcpy(tracen.data(), src->D.cs32 + CS_IDX(CS_TRACEN, 0, Cs), (size_t)Ts * 4,
+                         hipMemcpyDeviceToHost));
+      }
+      const uint32_t held = std::min(tracen[from], src->D.trace_cap);
+      // (a source past its own cap has dropped records a destination of another cap would hold)
+      if (tracen[from] > src->D.trace_cap && src->D.trace_cap != dst->D.trace_cap)
+        return set_err(at + ": the source drew " + std::to_string(tracen[from]) + " trace records past its "
+                       "trace_cap " + std::to_string(src->D.trace_cap) + ", the destination's is " +
+                       std::to_string(dst->D.trace_cap));
+      if (held > dst->D.trace_cap)
+        return set_err(at + ": the source holds " + std::to_string(held) +
+                       " trace records, the destination's trace_cap is " + std::to_string(dst->D.trace_cap));
+    }
+    any = true;
+  }
+  if (!any) return 0;  // nothing to copy: both batches stay bit for bit what they were
+  if ((d.flags & MR_F_RECORD) && !(s.flags & MR_F_RECORD))
+    return set_err("mr_batch_fork: a recording destination needs a recording source (MR_F_RECORD)");
+  // the message keys in HBM keep the format of the kernels that wrote them
+  const KeyFormat had = src->run.keys, next = key_format_of(dst->D);
+  if (had != KEYS_UNSET && (had != next || (dst->run.keys != KEYS_UNSET && dst->run.keys != had)))
+    return set_err(std::string("mr_batch_fork: source ran on ") + key_format_name(had) +
+                   ", destination continues on " + key_format_name(next) + " (another message-key format)");
+
+  const bool keep_tape = dst->dec.mode == OWN_RECORD && src->dec.mode == OWN_RECORD;
+  ForkPlan P{};
+  P.Cd = Cd; P.Cs = Cs;
+  uint64_t blocks = 0;
+  auto add = [&](ForkRow r) {
+    if (!r.owners || !r.dper || !r.sper) return true;
+    if (r.kind != FK_MINOR && ((r.dper | r.sper) & 15u)) return false;
+    r.blk0 = (uint32_t)blocks;
+    blocks += fork_blocks(r);
+    if (blocks >= (1ull << 31) || P.n_rows == FORK_ROWS) return false;
+    P.row[P.n_rows++] = r;
+    return true;
+  };
+  bool ok = true;
+  for (uint32_t a = 0; a < A__N && ok; a++) {
+    const OwnKind own = k_dev_own[a];
+    if (!own_is_cluster(own) || !dst->lay.bytes[a] || !src->lay.bytes[a]) continue;
+    if ((dst->lay.per[a] | src->lay.per[a]) >> 32) { ok = false; break; }
+    ForkRow r{};
+    r.dst = dst->base.get() + dst->lay.off[a];
+    r.src = src->base.get() + src->lay.off[a];
+    r.zfield = ~0u;
+    if (own == OWN_MINOR) {  // (n and msg_slots are equal: the same fields on both sides)
+      r.kind = FK_MINOR; r.owners = Cd; r.esz = k_dev_esz[a];
+      r.dper = r.sper = (uint32_t)(dst->lay.per[a] / r.esz);
+      if (src->lay.per[a] != dst->lay.per[a] || (r.esz != 4 && r.esz != 8)) { ok = false; break; }
+      if (a == A_cs32 && !keep_tape) r.zfield = CS_TAPE;  // no tape comes along: none drawn
+    } else {
+      r.kind = FK_MAJOR; r.owners = own == OWN_TRACED ? Td : Cd;
+      r.dper = (uint32_t)dst->lay.per[a]; r.sper = (uint32_t)src->lay.per[a];
+      if (own == OWN_MAJOR && r.dper != r.sper) { ok = false; break; }
+    }
+    ok = add(r);
+  }
+  if (ok && keep_tape) {  // the records drawn so far: a forked position's tape is its whole history
+    ForkRow r{};
+    r.dst = reinterpret_cast<char*>(dst->dec.tape.get());
+    r.src = reinterpret_cast<const char*>(src->dec.tape.get());
+    r.kind = FK_TAPE; r.owners = Cd; r.zfield = ~0u;
+    if (((uint64_t)dst->dec.dcap | src->dec.dcap) >> 28) ok = false;
+    r.dper = dst->dec.dcap * 16u; r.sper = src->dec.dcap * 16u;
+    P.tape_used = src->D.cs32 + CS_IDX(CS_TAPE, 0, Cs);
+    ok = ok && add(r);
+  }
+  if (!ok) return set_err("mr_batch_fork: the batches' arrays do not fit one fork launch");
+  P.blocks = (uint32_t)blocks;
+  DevMem<uint32_t> of_d;
+  if (const hipError_t e = upload(of_d, of.data(), of.size()); e != hipSuccess)
+    return set_err(std::string("mr_batch_fork: ") + hipGetErrorString(e));
+  P.src_of = of_d.get();
+  hipStream_t stream = dst->stream.get();
+  HIPCHK(hipEventRecord(dst->ev0.get(), stream));
+  HIPCHK(launch_fork(P, stream));
+  HIPCHK(hipEventRecord(dst->ev1.get(), stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  // the destination's launch loop starts over: a position with a verdict costs its lane one load
+  // (launch_begin / cluster_claim), whether the batch runs whole, in chunks or streaming
+  dst->run.c_open = 0;
+  dst->run.resume = false;
+  if (dst->run.keys == KEYS_UNSET) dst->run.keys = had;
+  dst->pg.fresh = false;
+  dst->fork_timed = true;
+  return 0;
+}
+
+int mr_batch_fork(mr_batch* dst, mr_batch* src, const uint32_t* src_of) {
+  if (!dst || !src || !src_of) return set_err("null argument");
+  if (dst->run.submitted || src->run.submitted)
+    return set_err("batch has a submitted step: mr_batch_finish it first");
+  HIPCHK(hipSetDevice(dst->cfg.device));
+  HIPCHK(hipStreamSynchronize(src->stream.get()));
+  HIPCHK(hipStreamSynchronize(dst->stream.get()));
+  return no_throw("mr_batch_fork", [&] { return fork_impl(dst, src, src_of); });
+}
+
+int mr_batch_fork_ms(mr_batch* b, float* ms) {
+  if (!b || !ms) return set_err("null argument");
+  if (!b->fork_timed) return set_err("mr_batch_fork_ms: the batch's last work was not a fork");
+  HIPCHK(hipSetDevice(b->cfg.device));
+  HIPCHK(hipEventElapsedTime(ms, b->ev0.get(), b->ev1.get()));
+  return 0;
 }
 
 int mr_replay(const mr_cfg* cfg, const mr_decision* d, size_t n, mr_event* out, size_t cap,

@@ -2604,6 +2604,7 @@ hipError_t launch_reduce(const Dev& D, unsigned long long* out, uint64_t cluster
   hipLaunchKernelGGL(reduce_kernel, grd, blk, 0, s, D, out, cluster_base);
   return hipGetLastError();
 }
+#include "mr_fork.inc"
 #endif  // MR_COMMON
 
 // the step kernel's dynamic LDS: the message keys, then the per-wave staging (lds_layout)

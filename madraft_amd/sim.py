@@ -68,6 +68,8 @@ def lib():
     L.mr_batch_group_counters.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MrCounters)]
     L.mr_batch_get_decisions_packed.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_size_t]
+    L.mr_batch_fork.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mr_batch_fork_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mr_decision_word.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     L.mr_decision_word.restype = C.c_uint32
     L.mr_replay.argtypes = [C.POINTER(MrCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
@@ -367,6 +369,22 @@ class Batch:
                      rec.size))
         return drawn, off, rec
 
+    def fork(self, src_of, src=None):
+        """Position c becomes a copy of position src_of[c] of batch `src` (None: this batch) as that
+        cluster stands now; _abi.FORK_SKIP leaves c as it is (mr_batch_fork; docs/SEMANTICS.md
+        §12.5). Its later draws follow c's own rule here, so its whole run equals the run of c's
+        seed with the source's decisions so far set as keyed decisions."""
+        of = np.ascontiguousarray(src_of, dtype=np.uint32)
+        if of.shape != (self.clusters,):
+            raise SimError(f"src_of: shape {of.shape}, not ({self.clusters},)")
+        _check(lib().mr_batch_fork(self._b, (src or self)._b, of.ctypes.data))
+
+    def fork_ms(self):
+        """Device time of this batch's last fork (mr_batch_fork_ms), before its next launch."""
+        ms = C.c_float()
+        _check(lib().mr_batch_fork_ms(self._b, C.byref(ms)))
+        return float(ms.value)
+
     def trace(self, k, cap=None):
         cap = cap or int(self.cfg.trace_cap)
         out = np.empty(cap, EVENT_DTYPE)
@@ -472,6 +490,48 @@ def run_seeds(test, seeds, **kw):
         cnt = b.counters()
     _print_failures(test, code, t, lambda k: seeds[k])
     return code, t, dig, cnt
+
+
+def run_futures(test, seed, at_events, futures, **kw):
+    """`futures` different continuations of one run of `seed`, from its state after `at_events`
+    events (docs/SEMANTICS.md §12.5). The seed is recorded up to there in a one-cluster MR_F_RECORD
+    batch, which gives the prefix tape P (a SimError if the seed already ended); a one-cluster
+    source of the futures' kernel family is brought to the same point (the recording batch itself
+    when the futures run a tape kernel); the source is forked into every position of a batch of
+    `futures` clusters, which runs to the end. Future c draws from the seed `seed` + cluster_base +
+    c after the prefix, and `replay(test, P, seed=seed, cluster_base=cluster_base + c, ...)`
+    reproduces it from scratch. Returns a dict: prefix (P), codes, times_us, digests, counters (a
+    prefix run on the pool kernel is counted in its source: mr_batch_fork) and kernel."""
+    seed, at_events, futures = int(seed), int(at_events), int(futures)
+    if at_events < 1 or futures < 1:
+        raise SimError("run_futures: at_events and futures must be >= 1")
+    kw = dict(kw)
+    base_c = int(kw.pop("cluster_base", 0))
+    flags = int(kw.pop("flags", 0)) & ~_abi.MR_F_RECORD
+    # (what sizes or schedules the futures' batch alone)
+    fut_kw = {k: kw.pop(k) for k in ("trace_clusters", "trace_cap", "lanes", "stream") if k in kw}
+    with Batch(test, 1, seed, cluster_base=base_c, flags=flags | _abi.MR_F_RECORD,
+               tape_cap=max(1 << 16, 64 * at_events), **kw) as rec, \
+            Batch(test, futures, seed, cluster_base=base_c, flags=flags, **fut_kw, **kw) as fut:
+        if rec.run(max_events=at_events)["remaining"] == 0:
+            raise SimError(f"run_futures: seed {seed + base_c} ended within {at_events} events")
+        n, prefix = rec.decisions(0)
+        if n > prefix.size:
+            raise SimError(f"run_futures: the prefix drew {n} decisions, the tape keeps {prefix.size}")
+        prefix = np.array(prefix)
+        of = np.zeros(futures, np.uint32)
+        if fut.kernel == "pool_kernel":  # a source whose message keys are the pool's
+            with Batch(test, 1, seed, cluster_base=base_c, flags=flags, **kw) as src:
+                if src.kernel != fut.kernel:
+                    raise SimError("run_futures: no one-cluster source on " + fut.kernel)
+                src.run(max_events=at_events)
+                fut.fork(of, src)
+        else:
+            fut.fork(of, rec)
+        fut.run()
+        code, t, dig = fut.verdicts()
+        return {"prefix": prefix, "codes": code, "times_us": t, "digests": dig,
+                "counters": fut.counters(), "kernel": fut.kernel}
 
 
 def sweep_groups(grid):
